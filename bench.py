@@ -13,8 +13,14 @@ Scenes shard over ranks with no data-path collective: every ran
 scenes (weak scaling); the collectives are the timing barrier, the max-over-ranks of the elapsed time and one
 all-reduce that proves RCCL saw N ranks.
 
-The K timed steps are bracketed by barrier + synchronize on both sides; that window is repeated `--windows` times and
-the MEDIAN window is reported (one host hiccup must not move the headline), every window's time is in the line.
+The K timed steps are bracketed by barrier + synchronize on both sides, and `ms_per_step` is that window's time over K.
+`--windows N` repeats the window N times and reports the MEDIAN one (one host hiccup must not move the headline); every
+window's time is in the line.  The default is one window, so that `--steps K` times exactly K steps.
+
+`--dump-outputs DIR` writes what the last timed step's forward returned, one DIR/<name>.npy per tensor of its output dict
+(float32; integer tensors as float64), at most 64 MB in all (beyond that, the same seeded sample of every tensor's elements).
+The inputs -- the synthetic batch, the weights (init_seed=0) and the Philox seed of every step -- follow from the arguments
+alone, so two builds run with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line: the throughput, the roofline of the dominant kernel (HIP events recorded inside the
 library on the launch stream during the timed region), the same workload on one stream, BASELINE configs[1]
@@ -53,8 +59,29 @@ FLOP_PER_EDGE = 41.7e3               # neighbour embed 25.1k + k
 MFMA_16BIT_PEAK_TFLOPS = 2500.0
 HBM_PEAK_GBS = 8000.0
 CPU_SAMPLE_SCENES = 1
+WARMUP_MIN_STEPS = 32                # untimed forwards before the timed window, whatever --warmup says (see main)
 DTYPE = {3: "f32 (fp16x3 split: 22-bit operands on v_mfma_f32_16x16x32_f16, f32 accumulate)",
          6: "f32 (bf16x6 split: 24-bit operands on v_mfma_f32_16x16x32_bf16, f32 accumulate)"}
+DUMP_LIMIT_BYTES = 60 << 20          # array data of --dump-outputs: with the .npy headers, under 64 MB (10^6 or 2^20 bytes)
+
+
+def dump_outputs(out, path):
+    """`--dump-outputs`: every tensor of the forward's output dict as <path>/<name>.npy, float32 (integers as float64, which
+    holds them exactly); if they exceed DUMP_LIMIT_BYTES together, each keeps the same seeded fraction of its flat elements"""
+    import numpy as np
+    import torch
+    arrs = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            a = v.detach().cpu().numpy()
+            arrs[k] = a.astype(np.float64 if np.issubdtype(a.dtype, np.integer) else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    for k, a in sorted(arrs.items()):
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(a.size * DUMP_LIMIT_BYTES / total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def spawn_ranks(args) -> int:
@@ -200,7 +227,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="timed K-step windows; the median one is reported")
+    ap.add_argument("--windows", type=int, default=1, help="timed K-step windows; the median one is reported")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("TRAJSDE_BENCH_STREAMS", "3")),
                     help="HIP streams the K steps are dealt over (each step is still one complete forward of one batch)")
@@ -211,7 +238,11 @@ def main():
     ap.add_argument("--strict24-child", default=None, metavar="NPY",
                     help="(internal) run as the child that times the 24-bit-operand library (TRAJSDE_LIB set by the parent) and "
                          "compares its trajectories with the parent's, saved in NPY")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step's forward returned as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.strict24_child:
         sys.exit(strict24_child(args))
 
@@ -299,31 +330,41 @@ def main():
         torch.cuda.synchronize()
 
     def timed_window(wl, steps, first, single_stream=False):
-        """EXACTLY `steps` forwards between barrier + synchronize on both sides; max over ranks"""
+        """EXACTLY `steps` forwards between barrier + synchronize on both sides; max over ranks.  Returns the time and what the
+        last forward returned (the others' outputs are released as they were before, step by step)"""
         sync_all()
         t0 = time.perf_counter()
-        for i in range(steps):
+        for i in range(steps - 1):
             wl.step(first + i, single_stream)
+        last = wl.step(first + steps - 1, single_stream)
         sync_all()
         el = time.perf_counter() - t0
         if dist is not None:
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el
+        return el, last
 
     wl = Workload(args.workload)
     with torch.no_grad():
         # W untimed steps -- and never fewer than two per stream: the first step of a stream sizes its buffers, the second is the
         # first to run while the previous one's buffers are still alive; leaving that to the timed region put a 100-200 ms
-        # allocator stall into its first window on some boxes
-        warm_steps = max(args.warmup, 2 * n_streams)
+        # allocator stall into its first window on some boxes.  And never fewer than WARMUP_MIN_STEPS: after 6 untimed steps the
+        # first 20-step window still ran 5% slower than the four after it (2.10 vs 1.99 ms/step), after 26 it did not -- the one
+        # timed window must not be that first one
+        warm_steps = max(args.warmup, 2 * n_streams, WARMUP_MIN_STEPS)
         for i in range(warm_steps):
             wl.step(i)
         sync_all()
         lib.trajsde_profile_mode(1)                                           # events around the dominant kernel only
-        windows = [timed_window(wl, args.steps, args.warmup + w * args.steps) for w in range(max(1, args.windows))]
+        n_windows = max(1, args.windows)
+        windows = [timed_window(wl, args.steps, args.warmup + w * args.steps)[0] for w in range(n_windows - 1)]
+        el_last, last_out = timed_window(wl, args.steps, args.warmup + (n_windows - 1) * args.steps)
+        windows.append(el_last)
         lib.trajsde_profile_mode(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
     prof = _lib.profile_report()
     e_aa = wl.e_aa()
     elapsed = float(np.median(windows))
@@ -335,7 +376,7 @@ def main():
         for i in range(2):
             wl.step(700 + i, single_stream=True)
         lib.trajsde_profile_mode(1)
-        w1 = [timed_window(wl, args.steps, 800 + w * args.steps, single_stream=True) for w in range(3)]
+        w1 = [timed_window(wl, args.steps, 800 + w * args.steps, single_stream=True)[0] for w in range(3)]
         lib.trajsde_profile_mode(0)
     iso_n, iso_ms, _ = _lib.profile_report().get("k_edge_kv[aa]", (0, 0.0, True))
     el1 = float(np.median(w1))
@@ -433,7 +474,7 @@ def main():
                 w2l = Workload(SECONDARY)
                 for i in range(2):
                     w2l.step(i)
-                w2 = [timed_window(w2l, args.steps, 100 + w * args.steps) for w in range(3)]
+                w2 = [timed_window(w2l, args.steps, 100 + w * args.steps)[0] for w in range(3)]
                 el2 = float(np.median(w2))
                 line["config2_64x128"] = {"value": w2l.scenes * args.steps / el2, "ms_per_step": 1e3 * el2 / args.steps, "unit": "scenes/s",
                                           "workload": "BASELINE configs[1]: 64 scenes x 128 agents, K=6, 20 SDE steps",

@@ -65,6 +65,33 @@ def maxdiff(a, b):
     return float((a.double() - b.double()).abs().max()) if a.numel() else 0.0
 
 
+def load_reference_call(name):
+    """tests/golden/reference_calls/<name>.npz (oracle/make_golden_reference_calls.py): what one of the reference's own
+    functions returned on stored or seeded inputs, as {key: tensor}"""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "reference_calls", name + ".npz"))
+    return {k: torch.from_numpy(z[k]) for k in z.files}
+
+
+def leave_only_agent_case():
+    """the collated batch (3 scenes, ragged lanes) and forward output that reference_calls/leave_only_agent.npz holds the
+    reference's `leave_only_agent` (MODEL:168-202) result for"""
+    from trajsde_amd.data import collate
+    from trajsde_amd.synth import synth
+    batch = collate([synth(S=1, n=n, L=L, F=5, box=60.0, seed=s) for n, L, s in ((5, 3, 1), (7, 4, 2), (4, 2, 3))])
+    N, K, T = batch["x"].shape[0], 2, 5
+    g = torch.Generator().manual_seed(0)
+    batch["rotate_mat"] = torch.randn(N, 2, 2, generator=g)
+    batch["has_goal"] = torch.arange(N) % 2 == 0
+    batch["goal_idcs"] = torch.arange(batch["lane_actor_index"].shape[1])
+    out = {"loc": torch.randn(K, N, T, 4, generator=g), "pi": torch.randn(N, K, generator=g),
+           "reg_mask": torch.rand(N, T, generator=g) > 0.3}
+    return batch, out
+
+
+LEAVE_ONLY_AGENT_KEYS = ("x", "y", "positions", "padding_mask", "bos_mask", "rotate_mat", "rotate_angles", "has_goal", "goal_idcs",
+                         "lane_actor_vectors", "lane_actor_index", "agent_index", "av_index", "batch")
+
+
 def reference_l2(y, loc, reg_mask):
     """losses/L2.py:10-27 spelled out on tensors (mean reduction)"""
     l2 = torch.norm(y.unsqueeze(0) - loc, p=2, dim=-1)

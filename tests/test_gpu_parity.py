@@ -333,6 +333,39 @@ def test_bench_spawned_rank_runs_the_rccl_path(tmp_path):
     assert line["config4_train"]["ms_per_step"] == ts["ms_per_step"] and line["config4_train"]["loss_L2"] > 0
 
 
+def test_bench_times_k_steps_and_dumps_the_last_one(tmp_path, dev):
+    """`bench.py --steps K --dump-outputs DIR`: one window of exactly K timed forwards, `ms_per_step` its time over K, and DIR
+    holds what the last of them returned, one float32 .npy per output tensor -- the same forward run here (the headline
+    workload, init_seed=0 weights, that step's Philox seed) gives the same arrays"""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet
+    from trajsde_amd.runtime import NoiseSpec
+    from trajsde_amd.synth import CONFIGS, synth
+    steps, warmup, out_dir = 3, 2, tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--no-cpu-baseline", "--no-secondary", "--no-train-step", "--dump-outputs", str(out_dir)],
+                       timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and len(line["timing"]["windows_ms"]) == 1
+    assert abs(line["ms_per_step"] - line["timing"]["windows_ms"][0] / steps) < 1e-9
+    spec = CONFIGS[bench.WORKLOAD]
+    model = PredictionModelSDENet(**bench.build_cfg(spec), init_seed=0).eval().to(dev)
+    with torch.no_grad():
+        want = model(synth(**spec["synth"]).to(dev), noise=NoiseSpec(seed=10_000 + warmup + steps - 1))
+    torch.cuda.synchronize()
+    want = {k: v.float().cpu() for k, v in want.items() if torch.is_tensor(v)}
+    assert sorted(p.name for p in out_dir.iterdir()) == sorted(k + ".npy" for k in want)
+    assert sum(p.stat().st_size for p in out_dir.iterdir()) <= 64 << 20
+    for k, v in want.items():
+        got = np.load(out_dir / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == tuple(v.shape), k
+        assert H.maxdiff(torch.from_numpy(got), v) <= 1e-5, k
+
+
 def test_dense_scene_1024_agents(dev):
     """stress shape of BASELINE config 5 (one 1024-agent scene, in-degree up to 1023, K=20, 50 -> 51 Euler steps):
     the segment softmax / CSR paths at maximum fan-in, checked against the oracle."""

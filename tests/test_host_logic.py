@@ -35,10 +35,8 @@ def test_losses_match_reference_formulas():
 
 
 def test_laplace_nll_value_matches_the_reference_class():
-    """losses/laplace_nll_loss.py evaluated by the reference's own class (run from /root/reference where it exists) and by the
-    literal formula otherwise"""
-    import os
-    import sys
+    """losses/laplace_nll_loss.py evaluated by the literal formula here, and by the reference's own class on the oracle's output
+    of the same case (tests/golden/reference_calls/laplace_nll.npz: its inputs and value, oracle/make_golden_reference_calls.py)"""
     from trajsde_amd.losses import LaplaceNLLLoss
     batch, o = _oracle_case()
     data = {"y": o["y"]}
@@ -52,11 +50,11 @@ def test_laplace_nll_value_matches_the_reference_class():
     l, s = loc[best, ar], scale[best, ar].clamp(min=1e-6)
     want = float((torch.log(2 * s) + torch.abs(o["y"] - l) / s)[o["reg_mask"]].mean())
     assert abs(got - want) <= 1e-6 * max(1.0, abs(want))
-    ref_file = "/root/reference/losses/laplace_nll_loss.py"
-    if os.path.isfile(ref_file):
-        from importlib.machinery import SourceFileLoader
-        ref = SourceFileLoader("ref_laplace", ref_file).load_module("ref_laplace").LaplaceNLLLoss(eps=1e-6)
-        assert abs(got - float(ref(data, {k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()}))) <= 1e-6 * max(1.0, abs(want))
+    ref = H.load_reference_call("laplace_nll")
+    ref_in = {k[3:]: v for k, v in ref.items() if k.startswith("in.")}
+    ref_want = float(ref["out.value"])
+    got_ref = float(LaplaceNLLLoss(eps=1e-6)({"y": ref_in["y"]}, ref_in))
+    assert abs(got_ref - ref_want) <= 1e-6 * max(1.0, abs(ref_want))
 
 
 def test_metrics_match_reference_formulas():

@@ -3,7 +3,7 @@ it to `pl.Trainer.fit / test`, which accept LightningModules only.  pytorch_ligh
 run a fresh interpreter with the build's stand-in package (oracle/shims/pytorch_lightning -- test infrastructure) importable:
 the class resolved through the registry must then BE a LightningModule, log what the reference's training_step logs, write the
 result file of `test_epoch_end` (MODEL:150-165) with the reference's keys, and `leave_only_agent` (MODEL:168-202) must cut a
-batch exactly like the reference's own static method does (run from /root/reference where that exists)."""
+batch exactly like the reference's own static method does (its result stored under tests/golden/reference_calls)."""
 import json
 import os
 import subprocess
@@ -97,31 +97,17 @@ def test_without_lightning_the_classes_are_plain_modules_with_the_same_hooks(tmp
 
 
 def test_leave_only_agent_cuts_the_batch_like_the_reference(tmp_path):
-    """MODEL:168-202 against the reference's own static method on the same collated batch (3 scenes, ragged lanes)"""
+    """MODEL:168-202 against what the reference's own static method left of the same collated batch (3 scenes, ragged lanes):
+    tests/golden/reference_calls/leave_only_agent.npz, made by oracle/make_golden_reference_calls.py"""
     import torch
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import ref_loader
-    if not ref_loader.reference_available():
-        pytest.skip("/root/reference is not here")
-    from trajsde_amd.data import collate
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers as H
     from trajsde_amd.models.lightning_base import LightningHooks
-    from trajsde_amd.synth import synth
-    batch = collate([synth(S=1, n=n, L=L, F=5, box=60.0, seed=s) for n, L, s in ((5, 3, 1), (7, 4, 2), (4, 2, 3))])
-    N, K, T = batch["x"].shape[0], 2, 5
-    g = torch.Generator().manual_seed(0)
-    batch["rotate_mat"] = torch.randn(N, 2, 2, generator=g)
-    batch["has_goal"] = torch.arange(N) % 2 == 0
-    batch["goal_idcs"] = torch.arange(batch["lane_actor_index"].shape[1])
-    out = {"loc": torch.randn(K, N, T, 4, generator=g), "pi": torch.randn(N, K, generator=g),
-           "reg_mask": torch.rand(N, T, generator=g) > 0.3}
-    ours_d, ours_o = __import__("helpers").clone_batch(batch), {k: v.clone() for k, v in out.items()}
+    ref = H.load_reference_call("leave_only_agent")
+    ours_d, ours_o = H.leave_only_agent_case()
     LightningHooks.leave_only_agent(ours_d, ours_o)
-    ref_model_cls = ref_loader.reference_model_class()
-    ref_d, ref_o = ref_loader.to_reference_data(batch), {k: v.clone() for k, v in out.items()}
-    ref_model_cls.leave_only_agent(ref_d, ref_o)
     for k in ("loc", "pi", "reg_mask"):
-        assert torch.equal(ours_o[k], ref_o[k]), k
-    for k in ("x", "y", "positions", "padding_mask", "bos_mask", "rotate_mat", "rotate_angles", "has_goal", "goal_idcs",
-              "lane_actor_vectors", "lane_actor_index", "agent_index", "av_index", "batch"):
-        assert torch.equal(ours_d[k], ref_d[k]), k
-    assert ours_d.num_nodes == ref_d.num_nodes
+        assert torch.equal(ours_o[k], ref["out." + k]), k
+    for k in H.LEAVE_ONLY_AGENT_KEYS:
+        assert torch.equal(ours_d[k], ref["data." + k]), k
+    assert ours_d.num_nodes == int(ref["num_nodes"])

@@ -85,9 +85,10 @@ def _stale() -> bool:
 
 
 def _run_all(jobs, what="hipcc"):
-    """run the compile commands, at most one per host core at a time (three builds of every unit started at once took ~3x the
-    peak host memory of one)"""
-    limit = max(2, os.cpu_count() or 2)
+    """run the compile commands, at most MAX_JOBS (when set) or one per core this process may run on at a time (three builds of
+    every unit started at once took ~3x the peak host memory of one; on a shared host os.cpu_count() is the whole machine's)"""
+    max_jobs = os.environ.get("MAX_JOBS", "")
+    limit = max(2, int(max_jobs) if max_jobs.isdigit() else len(os.sched_getaffinity(0)))
     pending, running, outputs = list(jobs), [], []
     while pending or running:
         while pending and len(running) < limit:
