@@ -73,7 +73,8 @@ typedef enum {
   TRAJSDE_STAGE_DECODER_MLP = 7,
   TRAJSDE_STAGE_DECODER_MLP_BWD = 8, /* trajsde_mlp_decoder_l2_backward; num_layers = future steps */
   TRAJSDE_STAGE_ENCODER_GRID_BWD = 9, /* trajsde_encoder_grid_backward; num_layers = temporal layers */
-  TRAJSDE_STAGE_DECODER_NLL_BWD = 10  /* trajsde_decoder_nll_backward: the DECODER_BWD table followed by the scale head (ABI 8) */
+  TRAJSDE_STAGE_DECODER_NLL_BWD = 10, /* trajsde_decoder_nll_backward: the DECODER_BWD table followed by the scale head (ABI 8) */
+  TRAJSDE_STAGE_DECODER_MILSTEIN = 11 /* trajsde_decoder_forward_milstein: the DECODER table; its blob + GFunc's transposes (ABI 10) */
 } trajsde_stage;
 
 int trajsde_param_count(int stage, int num_layers /*aggregator*/, int num_modes);
@@ -303,6 +304,15 @@ int trajsde_decoder_forward(int32_t N, int num_modes, int future_steps, const fl
                             const float* out_table /*[T,4] (steps_done,w0,w1,0)*/, float min_scale,
                             const trajsde_noise* noise /* z: [n_euler,K*N,64] */, void* ws, int64_t ws_bytes,
                             float* loc /*[K,N,T,4]*/, float* pi /*[N,K]*/, void* stream);
+/* Added at ABI 10: the same stage with the Milstein solve (torchsde MilsteinIto, `method: milstein`) instead of Euler-Maruyama:
+ * same parameters and workspace query (trajsde_decoder_ws_bytes), same schedule tables and noise (one normal row per step); `blob`
+ * is the TRAJSDE_STAGE_DECODER_MILSTEIN image (the decoder blob with GFunc's transposed matrices appended).  Inference only. */
+int trajsde_decoder_forward_milstein(int32_t N, int num_modes, int future_steps, const float* blob,
+                                     const float* local_embed /*[N,64]*/, const float* global_embed /*[K,N,64]*/,
+                                     const float* step_table /*[n_euler,8]*/, int n_euler,
+                                     const float* out_table /*[T,4] (steps_done,w0,w1,0)*/, float min_scale,
+                                     const trajsde_noise* noise /* z: [n_euler,K*N,64] */, void* ws, int64_t ws_bytes,
+                                     float* loc /*[K,N,T,4]*/, float* pi /*[N,K]*/, void* stream);
 
 /* ---- vanilla HiVT variant (configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml): LocalEncoder.forward
  *      (enc_hivt_nusargo_grid.py:52-93: AAEncoder, TemporalEncoder :225-292, ALEncoder; graph prepared with A = 0) and

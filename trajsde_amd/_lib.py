@@ -13,6 +13,7 @@ ALT_LIB_PATH = os.path.join(HERE, "variants", "libtrajsde_alt.so")
 STAGE_ENCODER, STAGE_AGGREGATOR, STAGE_DECODER, STAGE_DECODER_BWD, STAGE_AGGREGATOR_BWD, STAGE_ENCODER_BWD = 0, 1, 2, 3, 4, 5
 STAGE_ENCODER_GRID, STAGE_DECODER_MLP, STAGE_DECODER_MLP_BWD, STAGE_ENCODER_GRID_BWD = 6, 7, 8, 9
 STAGE_DECODER_NLL_BWD = 10
+STAGE_DECODER_MILSTEIN = 11   # trajsde_decoder_forward_milstein: the decoder blob + GFunc's transposed matrices (added at ABI 10)
 
 
 ABI_VERSION = 10         # trajsde_graph grew aa_src / la_lane (2); trajsde_dropout arguments (3); training tapes (4);
@@ -98,6 +99,7 @@ SIGNATURES = {
     "trajsde_aggregator_forward": (C.c_int, [C.POINTER(Batch), C.POINTER(Graph), P, C.c_int, C.c_int, P, P, I64, P, P]),
     "trajsde_decoder_ws_bytes": (I64, [I32, C.c_int]),
     "trajsde_decoder_forward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, C.c_int, P, F32, C.POINTER(Noise), P, I64, P, P, P]),
+    "trajsde_decoder_forward_milstein": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, C.c_int, P, F32, C.POINTER(Noise), P, I64, P, P, P]),
     "trajsde_decoder_backward_ws_bytes": (I64, [I32, C.c_int, C.c_int, C.c_int]),
     "trajsde_decoder_l2_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, C.POINTER(Noise), P, P, P, P, I64,
                                               P, P, C.POINTER(P), C.c_int, P, P, P]),

@@ -6,6 +6,9 @@
 //                 diffusion MLP weights + heads resident in LDS (~120 KB, fragment order), noise from
 //                 in-kernel Philox (or injected), time bookkeeping replayed from the float32 schedule table
 //                  so the micro-step of T in {30,50,60} is reproduced.
+//                 MIL = true (`method: milstein`, trajsde_decoder_forward_milstein): torchsde's MilsteinIto step instead -- the
+//                 same solve plus gdg = s (sum_i 0.5 v_i) ds/dy, ds/dy back-propagated through GFunc on the matrix cores
+//                 from GFunc's transposed matrices (layouts.hpp MilL, +32 KB of LDS; sde_funcs.hpp gfunc_input_grad).
 //   k_sde_step    the same step with the state round-tripping HBM (512 B / path-step), for the roofline report.
 #include <cstdlib>
 #include <type_traits>
@@ -87,14 +90,25 @@ __global__ __launch_bounds__(1024) void k_dec_init(const float* __restrict__ blo
   }
 }
 
-template <bool X6, int MAXT>
+// MIL: the Milstein step instead of Euler-Maruyama (the decoder's `method: milstein`); `blob` then points into a
+// TRAJSDE_STAGE_DECODER_MILSTEIN blob, whose Milstein image (MilL) follows the decoder blob and is staged right behind the decode image.
+template <bool X6, int MAXT, bool MIL = false>
 __global__ __launch_bounds__(MAXT) void k_sde_decode(const float* __restrict__ blob, const float* __restrict__ y0,
                                                      int64_t rows, int T, int n_euler,
                                                      const float* __restrict__ step_tab, const float* __restrict__ out_tab,
                                                      float min_scale, NoiseArg na, float* __restrict__ loc, int st_bf16) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using DL = typename std::conditional<X6, DecSdeL6, DecSdeL>::type;
-  stage_blob(lds, blob, DL::SIZE);
+  static_assert(!(MIL && X6) || TSDE_SPLIT_H3, "bf16x6: the split decode image and the Milstein image do not fit LDS together");
+  [[maybe_unused]] constexpr int IMG = DL::SIZE + (MIL ? int(MilL::SIZE) : 0);   // the per-wave time-bias slabs follow the image(s)
+  [[maybe_unused]] const float* mil = lds + DL::SIZE;
+  if constexpr (MIL) {
+    stage_copy(lds, blob, DL::SIZE);
+    stage_copy(lds + DL::SIZE, blob + (DecMilBlob::MIL - (X6 ? DecBlob::SDE6 : DecBlob::SDE)), MilL::SIZE);
+    __syncthreads();
+  } else {
+    stage_blob(lds, blob, DL::SIZE);
+  }
   const Lane L;
   const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6;
   const int64_t ntiles = (rows + 15) / 16;
@@ -115,17 +129,19 @@ __global__ __launch_bounds__(MAXT) void k_sde_decode(const float* __restrict__ b
       keep_lds_reads_here();
       const float dt = step_tab[k * 8 + 1], sq = step_tab[k * 8 + 2], sn = step_tab[k * 8 + 3], cs = step_tab[k * 8 + 4];
       f4 f[4], z[4];
+      [[maybe_unused]] f4 J[4];                                // (Milstein only: GFunc's input gradient without s (1 - s))
       float gs;
 #if TSDE_SPLIT_H3
       if constexpr (X6) {
         // this step's 128 first-layer biases, once per step in the wave's own LDS slot (they were 64 fma + 24 LDS reads per tile)
-        float* tb = lds + DL::SIZE + wave * 128;
+        float* tb = lds + IMG + wave * 128;
         __builtin_amdgcn_wave_barrier();                       // the previous step's reads of the slot are done (same wave, in order)
         sde_time_bias(tb, lds, sn, cs, L.lane);
         sde_time_bias(tb, lds, sn, cs, L.lane + 64);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        sde_fg_eval(f, gs, y, lds, tb, L);
+        if constexpr (MIL) sde_fg_eval_mil(f, gs, J, y, lds, tb, mil, L);
+        else sde_fg_eval(f, gs, y, lds, tb, L);
       } else
 #else
       if constexpr (X6) {
@@ -135,12 +151,14 @@ __global__ __launch_bounds__(MAXT) void k_sde_decode(const float* __restrict__ b
 #endif
       {
         drift_eval(f, y, lds + DL::F, sn, cs, L);
-        gs = diff_eval(y, lds + DL::G, sn, cs, L);
+        if constexpr (MIL) gs = diff_eval_mil(J, y, lds + DL::G, sn, cs, mil, L);
+        else gs = diff_eval(y, lds + DL::G, sn, cs, L);
       }
       noise_row(z, na, STREAM_DECODER, k, r, rows, L.g);
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt) prev[jt] = y[jt];
-      em_update(y, f, gs, z, dt, sq);
+      if constexpr (MIL) milstein_update(y, f, gs, J, z, dt, sq);
+      else em_update(y, f, gs, z, dt, sq);
       range_note(absmax<4>(y), RS_DEC_STATE);                 // the state is the next step's (and the heads') split operand
       // emit every output whose interpolation bracket closes with this step (linear_interp of the solver)
       while (o < T && int(out_tab[o * 4]) == k + 1) {
@@ -374,14 +392,10 @@ static NoiseArg to_arg(const trajsde_noise* n) {
   return a;
 }
 
-extern "C" {
-
-int64_t trajsde_decoder_ws_bytes(int32_t N, int num_modes) { return align_up(int64_t(N) * num_modes * 64 * 4, 256) + 256; }
-
-int trajsde_decoder_forward(int32_t N, int num_modes, int future_steps, const float* blob, const float* local_embed,
-                            const float* global_embed, const float* step_table, int n_euler, const float* out_table,
-                            float min_scale, const trajsde_noise* noise, void* ws, int64_t ws_bytes, float* loc,
-                            float* pi, void* stream_) {
+static int decoder_forward(bool milstein, int32_t N, int num_modes, int future_steps, const float* blob, const float* local_embed,
+                           const float* global_embed, const float* step_table, int n_euler, const float* out_table,
+                           float min_scale, const trajsde_noise* noise, void* ws, int64_t ws_bytes, float* loc,
+                           float* pi, void* stream_) {
   TS_REQUIRE(blob && local_embed && global_embed && step_table && out_table && loc && pi && ws, "decoder_forward: null pointer");
   TS_REQUIRE(N > 0 && num_modes > 0 && future_steps > 0 && n_euler > 0, "decoder_forward: empty problem");
   if (ws_bytes < trajsde_decoder_ws_bytes(N, num_modes)) return fail(TRAJSDE_ERR_WORKSPACE, "decoder_forward: workspace too small");
@@ -406,6 +420,27 @@ int trajsde_decoder_forward(int32_t N, int num_modes, int future_steps, const fl
 #define TS_DECODE(X6, MAXT, IMG, OFF, DT)                                                                                      \
   TS_LAUNCH((k_sde_decode<X6, MAXT>), pick_grid(ntiles, (DT) / 64), (DT), (IMG::SIZE + ((DT) / 64) * 128) * 4, stream, blob + OFF, y0, rows, \
             future_steps, n_euler, step_table, out_table, min_scale, to_arg(noise), loc, state_bf16() ? 1 : 0)
+  if (milstein) {
+    // Milstein (blob: the TRAJSDE_STAGE_DECODER_MILSTEIN image): MilL staged behind the decode image, the time-bias slabs behind both
+    // (fp16x3: 149 KB + 12 slabs = 155 KB, still 768 threads).  GFunc's activations and the input gradient J live across the step:
+    // 146 / 157 VGPRs (split / plain image), inside the 768-thread build's 168.  The bf16x6 build's split image does not fit beside MilL
+    // (157 + 32 KB): the plain-image form there, and only its 512-thread (256-VGPR) build -- 242 VGPRs (its Euler 768 build spills).
+#define TS_DECODE_MIL(X6, MAXT, IMG, OFF, DT)                                                                                        \
+  TS_LAUNCH((k_sde_decode<X6, MAXT, true>), pick_grid(ntiles, (DT) / 64), (DT), (IMG::SIZE + MilL::SIZE + ((DT) / 64) * 128) * 4, stream, \
+            blob + OFF, y0, rows, future_steps, n_euler, step_table, out_table, min_scale, to_arg(noise), loc, state_bf16() ? 1 : 0)
+    const int dm1 = fit(DecSdeL::SIZE + MilL::SIZE);
+#if TSDE_SPLIT_H3
+    const int dm6 = fit(DecSdeL6::SIZE + MilL::SIZE);
+    if (x6 && dm6 <= 512) TS_DECODE_MIL(true, 512, DecSdeL6, DecBlob::SDE6, dm6);
+    else if (x6) TS_DECODE_MIL(true, 768, DecSdeL6, DecBlob::SDE6, dm6);
+    else if (dm1 <= 512) TS_DECODE_MIL(false, 512, DecSdeL, DecBlob::SDE, dm1);
+    else TS_DECODE_MIL(false, 768, DecSdeL, DecBlob::SDE, dm1);
+#else
+    TS_DECODE_MIL(false, 512, DecSdeL, DecBlob::SDE, dm1 < 512 ? dm1 : 512);
+#endif
+#undef TS_DECODE_MIL
+    return TRAJSDE_OK;
+  }
   const int dt6 = fit(DecSdeL6::SIZE), dt1 = fit(DecSdeL::SIZE);
   if (x6 && dt6 <= 512) TS_DECODE(true, 512, DecSdeL6, DecBlob::SDE6, dt6);
   else if (x6) TS_DECODE(true, 768, DecSdeL6, DecBlob::SDE6, dt6);
@@ -413,6 +448,26 @@ int trajsde_decoder_forward(int32_t N, int num_modes, int future_steps, const fl
   else TS_DECODE(false, 768, DecSdeL, DecBlob::SDE, dt1);
 #undef TS_DECODE
   return TRAJSDE_OK;
+}
+
+extern "C" {
+
+int64_t trajsde_decoder_ws_bytes(int32_t N, int num_modes) { return align_up(int64_t(N) * num_modes * 64 * 4, 256) + 256; }
+
+int trajsde_decoder_forward(int32_t N, int num_modes, int future_steps, const float* blob, const float* local_embed,
+                            const float* global_embed, const float* step_table, int n_euler, const float* out_table,
+                            float min_scale, const trajsde_noise* noise, void* ws, int64_t ws_bytes, float* loc,
+                            float* pi, void* stream_) {
+  return decoder_forward(false, N, num_modes, future_steps, blob, local_embed, global_embed, step_table, n_euler, out_table, min_scale, noise,
+                         ws, ws_bytes, loc, pi, stream_);
+}
+
+int trajsde_decoder_forward_milstein(int32_t N, int num_modes, int future_steps, const float* blob, const float* local_embed,
+                                     const float* global_embed, const float* step_table, int n_euler, const float* out_table,
+                                     float min_scale, const trajsde_noise* noise, void* ws, int64_t ws_bytes, float* loc,
+                                     float* pi, void* stream_) {
+  return decoder_forward(true, N, num_modes, future_steps, blob, local_embed, global_embed, step_table, n_euler, out_table, min_scale, noise,
+                         ws, ws_bytes, loc, pi, stream_);
 }
 
 int trajsde_sde_step(int32_t rows, const float* blob, const float* y_in, float* y_out, const float* e, int step,

@@ -335,6 +335,20 @@ static_assert(DecSdeL6::SIZE * 4 <= 160 * 1024, "split-precision decoder image m
 struct DecBlob {
   enum : int { INIT = 0, SDE = INIT + DecInitL::SIZE, SDE6 = SDE + DecSdeL::SIZE, SIZE = SDE6 + DecSdeL6::SIZE };
 };
+// Milstein decode (k_sde_decode_milstein): GFunc's inner matrices TRANSPOSED and UNSCALED -- the y-columns of net.0 and net.2, as the
+// backward sweep packs them (SweepL G_W0T / G_W2T) -- for the input gradient ds/dy of the diffusion (sde_funcs.hpp gfunc_input_grad).
+// The TRAJSDE_STAGE_DECODER_MILSTEIN blob is the decoder blob with this image appended: the Euler launches read the same bytes as
+// ever, and in LDS the image sits right behind the decode image (which is the last one of DecBlob: contiguous for the fp16x3 form).
+struct MilL {
+  enum : int { S_END = 0, TS_FIELD(G_W0T, MAT64, S), TS_FIELD(G_W2T, MAT64, G_W0T), SIZE = G_W2T_END };
+};
+struct DecMilBlob {
+  enum : int { MIL = DecBlob::SIZE, SIZE = MIL + MilL::SIZE };
+};
+static_assert(DecMilBlob::MIL % 4 == 0 && (DecSdeL::SIZE + MilL::SIZE) * 4 <= 160 * 1024, "Milstein image: aligned, fits LDS");
+#if TSDE_SPLIT_H3
+static_assert((DecSdeL6::SIZE + MilL::SIZE) * 4 <= 160 * 1024, "fp16x3 decode image + Milstein image must fit LDS");
+#endif
 
 // ---- vanilla HiVT variant (grid.hip): TemporalEncoder (GENC:241-292) and MLPDecoder (GDEC:11-63)
 struct TrOutL {       // self_attn.out_proj + norm2

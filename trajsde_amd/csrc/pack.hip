@@ -860,6 +860,13 @@ static void recipe_decoder(Packer& P) {
 #endif
 }
 
+// Milstein decode: the decoder's table and images, then GFunc's net.0 (y-columns) and net.2 transposed, unscaled (layouts.hpp MilL)
+static void recipe_decoder_milstein(Packer& P) {
+  recipe_decoder(P);
+  P.matT("lsde_func.g_func.net.0.weight", DecMilBlob::MIL + MilL::G_W0T, 66);
+  P.matT("lsde_func.g_func.net.2.weight", DecMilBlob::MIL + MilL::G_W2T, 64);
+}
+
 static void recipe_aggr_embed_bwd(Packer& P, int b) {      // aggr_embed of either decoder: forward halves + transposes
   using I = InitBwdL;
   P.mat("aggr_embed.0.weight", b + I::WA_G, 64, 64, 128, 0);
@@ -1067,6 +1074,7 @@ static bool run_recipe(Packer& P, int stage, int nl, int K) {
     case TRAJSDE_STAGE_ENCODER: recipe_encoder(P); return true;
     case TRAJSDE_STAGE_AGGREGATOR: recipe_aggregator(P, nl, K); return true;
     case TRAJSDE_STAGE_DECODER: recipe_decoder(P); return true;
+    case TRAJSDE_STAGE_DECODER_MILSTEIN: recipe_decoder_milstein(P); return true;
     case TRAJSDE_STAGE_DECODER_BWD: recipe_decoder_bwd(P); return true;
     case TRAJSDE_STAGE_DECODER_NLL_BWD: recipe_decoder_nll_bwd(P); return true;
     case TRAJSDE_STAGE_AGGREGATOR_BWD: recipe_aggregator_bwd(P, nl, K); return true;
@@ -1200,6 +1208,7 @@ int64_t trajsde_blob_floats(int stage, int num_layers, int num_modes) {
     case TRAJSDE_STAGE_ENCODER: return EncBlob::SIZE;
     case TRAJSDE_STAGE_AGGREGATOR: return AggBlob::size(num_layers, num_modes);
     case TRAJSDE_STAGE_DECODER: return DecBlob::SIZE;
+    case TRAJSDE_STAGE_DECODER_MILSTEIN: return DecMilBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_BWD: return DecBwdBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_NLL_BWD: return DecNllBwdBlob::SIZE;
     case TRAJSDE_STAGE_AGGREGATOR_BWD: return AggBwdBlob::size(num_layers, num_modes);

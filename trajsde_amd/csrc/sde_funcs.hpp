@@ -109,4 +109,84 @@ __device__ __forceinline__ void sde_fg_eval(f4 (&f)[4], float& gs, const f4 (&y)
 }
 #endif
 
+// ---- Milstein step (torchsde MilsteinIto with the default grad_free=False) for the decoder's scalar-broadcast diffusion
+// g(y) = s(y) 1.  torchsde's g_prod_and_gdg_prod_diagonal takes vjp(g, y, g * 0.5 v): with g one scalar repeated over the 64
+// channels that is a COLUMN SUM, not the textbook diagonal term,
+//   gdg_j = s (sum_i 0.5 v_i) ds/dy_j,   ds/dy = s (1 - s) W0y^T ((1 - h1^2) . W2^T ((1 - h2^2) . w4))
+// (h1, h2 the two tanh activations of GFunc, W0y the y-columns of net.0, w4 = net.4.weight).
+// J = the bracket W0y^T (...) (without s (1 - s), a per-row scalar applied in milstein_update).  Its two products run on the transposed,
+// UNSCALED images of MilL (the fp16x3 forward image carries 2 / ln 2 in front of each tanh: not these) through linear_adj, whose
+// row-scaled split keeps small rows (w4 and the tanh derivatives) out of the fp16 subnormals.
+__device__ __forceinline__ void gfunc_input_grad(f4 (&J)[4], const f4 (&h1)[4], const f4 (&h2)[4], const float* w4, const float* mil,
+                                                 const Lane& L) {
+  f4 a[4], d[4];
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt) {
+    const f4 w = *reinterpret_cast<const f4*>(w4 + 16 * jt + 4 * L.g);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[jt][c] = fmaf(-h2[jt][c], h2[jt][c], 1.0f) * w[c];
+    d[jt] = f4{0.f, 0.f, 0.f, 0.f};
+    J[jt] = f4{0.f, 0.f, 0.f, 0.f};
+  }
+  linear_adj<4, 4>(d, a, mil + MilL::G_W2T, L);
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) d[jt][c] *= fmaf(-h1[jt][c], h1[jt][c], 1.0f);
+  linear_adj<4, 4>(J, d, mil + MilL::G_W0T, L);
+}
+
+// y1 = y + f dt + g I + gdg,  I = z sqrt_h,  v = I^2 - dt   (MilsteinIto.step; v_term)
+__device__ __forceinline__ void milstein_update(f4 (&y)[4], const f4 (&f)[4], float gs, const f4 (&J)[4], const f4 (&z)[4], float dt,
+                                                float sq) {
+  float hv = 0.f;
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float I = z[jt][c] * sq;
+      hv += fmaf(I, I, -dt);
+    }
+  const float coef = gs * (0.5f * row_sum(hv)) * (gs * (1.0f - gs));      // s (sum_i 0.5 v_i) s (1 - s)
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) y[jt][c] = fmaf(coef, J[jt][c], (y[jt][c] + f[jt][c] * dt) + gs * (z[jt][c] * sq));
+}
+
+// diffusion of the plain image (DiffL) that also returns J (above)
+__device__ __forceinline__ float diff_eval_mil(f4 (&J)[4], const f4 (&y)[4], const float* img, float sn, float cs, const float* mil,
+                                               const Lane& L) {
+  f4 h1[4], h2[4];
+  sde_layer0(h1, y, img, DiffL::W0, DiffL::WS, DiffL::WC, DiffL::B0, sn, cs, L);
+  tanh_<4>(h1);
+  linear<4, 4>(h2, h1, img + DiffL::W2, img + DiffL::B2, L);
+  tanh_<4>(h2);
+  const float s = fast_sigmoid(row_dot(h2, img + DiffL::W4, L.g) + img[DiffL::B4]);
+  gfunc_input_grad(J, h1, h2, img + DiffL::W4, mil, L);
+  return s;
+}
+
+#if TSDE_SPLIT_H3
+// sde_fg_eval (same products, same order, same f and s) that keeps GFunc's activations and returns J as well
+__device__ __forceinline__ void sde_fg_eval_mil(f4 (&f)[4], float& gs, f4 (&J)[4], const f4 (&y)[4], const float* img, const float* tb,
+                                                const float* mil, const Lane& L) {
+  using DD = DecSdeL6;
+  f4 h[8];
+#pragma unroll
+  for (int jo = 0; jo < 8; ++jo) h[jo] = *reinterpret_cast<const f4*>(tb + 16 * jo + 4 * L.g);
+  linear_acc_x6<8, 4>(h, y, img + DD::W0FG, L.lane);
+  tanh_prescaled_<8>(h);
+  const f4 hf[4] = {h[0], h[1], h[2], h[3]}, hg[4] = {h[4], h[5], h[6], h[7]};
+  f4 h2[4];
+  linear_x6<4, 4>(h2, hf, img + DD::F_W2, img + DD::F_B2, L);
+  tanh_prescaled_<4>(h2);
+  linear_x6<4, 4>(f, h2, img + DD::F_W4, img + DD::F_B4, L);
+  linear_x6<4, 4>(h2, hg, img + DD::G_W2, img + DD::G_B2, L);
+  tanh_prescaled_<4>(h2);                                  // (tanh of the true pre-activation: h1, h2 are GFunc's own activations)
+  gs = fast_sigmoid(row_dot(h2, img + DD::G_W4, L.g) + img[DD::G_B4]);
+  gfunc_input_grad(J, hg, h2, img + DD::G_W4, mil, L);
+}
+#endif
+
 }  // namespace tsde

@@ -1,7 +1,9 @@
 """SDEDecoder -- MI355X path of models/decoders/dec_hivt_nusargo_sde.py:14-105: fuse local+global
 embeddings into y0 [K*N,64], Euler-Maruyama over the future grid with learned drift and
-scalar-broadcast diffusion, heads -> loc/scale/pi.
+scalar-broadcast diffusion (Euler-Maruyama or Milstein), heads -> loc/scale/pi.
 
+`method: euler` (the shipped one) or `method: milstein` (torchsde's MilsteinIto: the same fixed-step schedule and noise, plus the
+column-sum gdg term of the scalar-broadcast diffusion; inference only -- training refuses it).
 Constructor kwargs as in configs/nusargo/hivt_nuSArgo_sdesepenc_sdedec.yml:64-76; call signature
 `decoder(data=..., local_embed=..., global_embed=...) -> {'loc','pi','reg_mask'}`; `uncertain: False` (DEC:56, DEC:100-101):
 no `scale.*` parameters and `loc` [K, N, T, 2] -- the kernels run with a zero stand-in head and the scale channels are dropped.
@@ -10,6 +12,23 @@ from typing import Optional
 
 from trajsde_amd.models.params import ParamTree
 from trajsde_amd import runtime
+from trajsde_amd.schedule import ITO_METHODS, SDE_METHODS
+
+
+def check_method(method):
+    """the decoder's `method` kwarg, handed to stock torchsde.sdeint (DEC:88): `euler` and `milstein` are built (MilsteinIto with
+    its default grad_free=False; csrc/decoder.hip); everything else is refused the way torchsde would, or as not built"""
+    if method is None:
+        raise NotImplementedError("method=None: torchsde then picks srk for this Ito SDE with diagonal noise, which is not built "
+                                  "(srk needs the space-time Levy area, a second random stream the Philox noise model does not have)")
+    if method not in SDE_METHODS:
+        raise ValueError(f"Expected method in {SDE_METHODS}, but found {method}.")
+    if method not in ITO_METHODS:
+        raise ValueError(f"method {method!r} is a Stratonovich solver: torchsde does not accept it for this Ito SDE")
+    if method == "srk":
+        raise NotImplementedError("method='srk' is not built: it needs the space-time Levy area, a second random stream the Philox "
+                                  "noise model does not have (built: euler, milstein)")
+    return method
 
 
 class SDEDecoder(ParamTree):
@@ -20,8 +39,9 @@ class SDEDecoder(ParamTree):
             setattr(self, key, value)
         self.input_size, self.hidden_size = self.global_channels, self.local_channels
         d = self.hidden_size
-        if d != 64 or self.input_size != 64 or self.method != "euler":
-            raise NotImplementedError("kernels are specialised for 64 channels, euler (CFG:64-76)")
+        if d != 64 or self.input_size != 64:
+            raise NotImplementedError("kernels are specialised for 64 channels (CFG:64-76)")
+        self.method = check_method(getattr(self, "method", None))
         self.linear("aggr_embed.0", d, self.input_size + d)
         self.layernorm("aggr_embed.1", d)
         self.sde_nets("lsde_func", d, ("g_func",))

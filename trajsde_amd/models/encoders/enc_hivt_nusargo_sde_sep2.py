@@ -13,6 +13,7 @@ import torch
 
 from trajsde_amd.models.params import ParamTree
 from trajsde_amd import runtime
+from trajsde_amd.schedule import SDE_METHODS
 
 
 class LocalEncoderSDESepPara2(ParamTree):
@@ -23,8 +24,12 @@ class LocalEncoderSDESepPara2(ParamTree):
             setattr(self, key, value)
         if not self.parallel:
             raise NotImplementedError("parallel=False is not implemented (reference: ENC:122-123)")
-        if not self.run_backwards or self.method != "euler" or self.adaptive or self.sde_layers != 2:
-            raise NotImplementedError("only the shipped solver settings are built: euler, fixed step, "
+        method = getattr(self, "method", None)
+        if method is not None and method not in SDE_METHODS:       # the reference's sdeint_dual checks the name (SDEINT:870-871) ...
+            raise ValueError(f"Expected method in {SDE_METHODS}, but found {method}.")
+        # ... and then runs Euler_private whatever the name (SDEINT:177-182): so does this encoder
+        if not self.run_backwards or self.adaptive or self.sde_layers != 2:
+            raise NotImplementedError("only the shipped solver settings are built: fixed step, "
                                       "run_backwards, sde_layers=2 (CFG:37-46)")
         d, h = self.embed_dim, self.historical_steps
         if d != 64 or self.num_heads != 8 or self.node_dim != 2 or self.edge_dim != 2:

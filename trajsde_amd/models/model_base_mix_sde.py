@@ -308,7 +308,8 @@ class PredictionModelSDENet(LightningHooks):
         reference's sites (attention weights, out_proj output, the two FFN activations of every attention block) with masks
         cut from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()` switches it off, as in the reference.  The kernels implement the
         shipped loss set (losses/L2.py + losses/diff_BCE.py, CFG:78-83) and losses/laplace_nll_loss.py in place of L2; any other loss
-        is refused rather than silently differentiated elsewhere."""
+        is refused rather than silently differentiated elsewhere.  So is a decoder with `method: milstein` (inference only)."""
+        runtime.refuse_milstein_training(self.decoder)
         if not self.rotate:
             raise NotImplementedError("rotate=False is not built (shipped config: rotate: true, CFG:18)")
         if not getattr(self.decoder, "uncertain", True):

@@ -467,6 +467,13 @@ class PackSet:
             rt._blobs[sid] = (blob, stamp, ev, cur.cuda_stream)
 
 
+def refuse_milstein_training(decoder) -> None:
+    """the Milstein decoder is built for inference: differentiating its gdg term needs Hessian-vector products of GFunc"""
+    if getattr(decoder, "method", "euler") == "milstein":
+        raise NotImplementedError("training a decoder with `method: milstein` is not built: the gradient of its gdg term needs "
+                                  "Hessian-vector products of GFunc (inference is supported)")
+
+
 class StageRuntime:
     """Per-stage glue owned by a stage module (encoder / aggregator / decoder)."""
 
@@ -610,17 +617,21 @@ class StageRuntime:
         if noise.z_dec is not None and tuple(noise.z_dec.shape) != (sched.n_euler, K * N, D):
             raise _lib.TrajsdeError(f"z_dec must be [{sched.n_euler},{K * N},{D}] (one increment per Euler step, App. D)")
         L = _lib.lib()
-        blob = self.blob()
+        # `method` (SDEDecoder checks it): euler, or milstein -- the same call on the Milstein image (the decoder blob + GFunc's transposes)
+        if m.method == "milstein":
+            blob, entry, name = self.blob(_lib.STAGE_DECODER_MILSTEIN), L.trajsde_decoder_forward_milstein, "trajsde_decoder_forward_milstein"
+        else:
+            blob, entry, name = self.blob(), L.trajsde_decoder_forward, "trajsde_decoder_forward"
         loc = torch.empty(K, N, T, 4, device=dev, dtype=torch.float32)
         pi = torch.empty(N, K, device=dev, dtype=torch.float32)
         ws_bytes = L.trajsde_decoder_ws_bytes(N, K)
         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
         with torch.cuda.device(dev):
-            _lib.check(L.trajsde_decoder_forward(N, K, T, blob.data_ptr(), local_embed.contiguous().data_ptr(),
-                                                 global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler,
-                                                 out_tab.data_ptr(), float(m.min_scale), C.byref(cn), ws.data_ptr(), ws_bytes,
-                                                 loc.data_ptr(), pi.data_ptr(), _stream()), "trajsde_decoder_forward")
+            _lib.check(entry(N, K, T, blob.data_ptr(), local_embed.contiguous().data_ptr(),
+                             global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler,
+                             out_tab.data_ptr(), float(m.min_scale), C.byref(cn), ws.data_ptr(), ws_bytes,
+                             loc.data_ptr(), pi.data_ptr(), _stream()), name)
         out = {"loc": loc, "pi": pi, "reg_mask": ~data["padding_mask"][:, -T:]}          # DEC:104
         _drop_scale_channels(m, out)
         return out
@@ -643,6 +654,7 @@ class StageRuntime:
     def _decoder_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
                           noise: NoiseSpec, nll_eps: Optional[float]) -> Dict[str, object]:
         """shared body of decoder_l2_backward / decoder_nll_backward (`nll_eps` None: L2)"""
+        refuse_milstein_training(self.module)
         m = self.module
         if noise is None:
             raise _lib.TrajsdeError("decoder_l2_backward needs the NoiseSpec of the forward pass (seed or z_dec)")

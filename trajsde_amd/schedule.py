@@ -107,3 +107,9 @@ def encoder_schedule(historical_steps: int = 21, max_past_t: float = 2.0, dt: fl
     return EulerSchedule(t0=cat("t0"), dt=cat("dt"), sqrt_h=cat("sqrt_h"), sin_t0=cat("sin_t0"), cos_t0=cat("cos_t0"),
                          out_step=np.concatenate([p.out_step + o for p, o in zip(parts, steps_before)]).astype(np.int32),
                          out_w0=cat("out_w0"), out_w1=cat("out_w1"))
+
+
+# torchsde 0.2.5 settings.METHODS (the `method` names sdeint accepts at all) and the ones it accepts for an Ito SDE such as the
+# encoder's and the decoder's (diagonal noise); the others are Stratonovich solvers
+SDE_METHODS = ("euler", "milstein", "srk", "midpoint", "reversible_heun", "adjoint_reversible_heun", "heun", "log_ode", "euler_heun")
+ITO_METHODS = ("euler", "milstein", "srk")
