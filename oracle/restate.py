@@ -1,6 +1,7 @@
 """CPU restatement of TrajSDE's forward hot path -- TEST INFRASTRUCTURE ONLY.
 
-Plain torch fp32 on the host.  This file is the *checker*: only tests/, __graft_entry__.smoke() and
+Plain torch on the host, in the dtype of the weights and the batch (fp32 for the fixtures, float64 as a reference for the
+kernels' own error: tests/helpers.py oracle_forward64).  This file is the *checker*: only tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg may import it.  The product path (trajsde_amd/) never does.
 
 Parity pin: validated <= 1e-5 against golden vectors produced by running the reference's own modules
@@ -241,7 +242,7 @@ def local_encoder(P, cfg, batch, rot, noise, enc_sched, want_intermediates=False
         t = H - 1 - idx
         s_t, c_t = float(enc_sched.sin_t0[idx]), float(enc_sched.cos_t0[idx])
         f = drift(P, lf + ".f_func", h, s_t, c_t)
-        g = torch.empty(Nt, D)
+        g = h.new_empty(Nt, D)
         g[nus_mask] = diffusion(P, lf + ".g_nus", h[nus_mask], s_t, c_t).repeat(1, D)      # ENC:470-482
         g[~nus_mask] = diffusion(P, lf + ".g_argo", h[~nus_mask], s_t, c_t).repeat(1, D)
         dW = noise.encoder(idx, (Nt, D)) * float(enc_sched.sqrt_h[idx])
@@ -318,13 +319,13 @@ def local_encoder_ood(P, cfg, batch, rot, noise, enc_sched, eval_iter=10):
     lf = pre + ".lsde_func"
     outs = []
     for j in range(eval_iter):                                              # ENC:255-309
-        h = torch.zeros(N, D)
+        h = x.new_zeros(N, D)
         latent = []
         for idx in range(H):
             t = H - 1 - idx
             s_t, c_t = float(enc_sched.sin_t0[idx]), float(enc_sched.cos_t0[idx])
             f = drift(P, lf + ".f_func", h, s_t, c_t)
-            g = torch.empty(N, D)
+            g = h.new_empty(N, D)
             g[nus_mask] = diffusion(P, lf + ".g_nus", h[nus_mask], s_t, c_t).repeat(1, D)
             g[~nus_mask] = diffusion(P, lf + ".g_argo", h[~nus_mask], s_t, c_t).repeat(1, D)
             dW = noise.encoder(j * H + idx, (N, D)) * float(enc_sched.sqrt_h[idx])

@@ -61,6 +61,77 @@ def oracle_forward(model, cfg, batch, noise_seed, want_intermediates=True):
                            want_intermediates=want_intermediates)
 
 
+def double_batch(batch):
+    b = clone_batch(batch).to("cpu")
+    for k in b.keys:
+        if torch.is_tensor(b[k]) and b[k].is_floating_point():
+            b[k] = b[k].double()
+    return b
+
+
+class Float64Noise:
+    """a restate noise source whose float32 normals (the Philox stream the kernels draw, or injected ones) are handed on as float64:
+    the same numbers, so that a float64 oracle run differs from the kernels only by their arithmetic"""
+
+    def __init__(self, inner):
+        self.inner = inner
+
+    def fake_agent(self, shape):
+        return self.inner.fake_agent(shape).detach().cpu().double()
+
+    def encoder(self, idx, shape):
+        return self.inner.encoder(idx, shape).detach().cpu().double()
+
+    def decoder(self, k, shape):
+        return self.inner.decoder(k, shape).detach().cpu().double()
+
+
+def oracle_forward64(model, cfg, batch, noise_seed=None, noise=None, want_intermediates=True, ood=False, drop=None):
+    """oracle_forward in float64: the parameters and the batch's floating tensors cast to double, the fp32 normals of Philox seed
+    `noise_seed` (or the restate noise source `noise`, e.g. restate.InjectedNoise) taken as they are.  Outputs are float64."""
+    import restate
+    P = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
+    src = restate.PhiloxNoise(int(noise_seed)) if noise is None else noise
+    return restate.forward(P, cfg, double_batch(batch), Float64Noise(src), want_intermediates=want_intermediates, ood=ood, drop=drop)
+
+
+def trained_like_parameters(model, seed, strength=1.0):
+    """move every trainable parameter away from the initial point the way training does, so that the biases, LayerNorm affines,
+    tokens and hidden vectors the kernels fold into their weight images (csrc/pack.hip) are no longer 0 / 1: with one normal
+    draw z per entry, from one CPU generator in parameters() order,
+      matrices           W <- W * (1 + 0.3 s |z|)
+      biases (LN too)    b <- 0.3 s z
+      LayerNorm gamma    g <- 1 + 0.4 s z        (some entries negative)
+      tokens, hidden     t <- t + 0.3 s z
+    with s = `strength`.  The frozen prior constants (h_func) are left alone.  Writes go through the parameters themselves (not
+    `.data`), so their version counters move and the next forward re-packs."""
+    g = torch.Generator().manual_seed(int(seed))
+    s = float(strength)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if not p.requires_grad:
+                continue
+            z = torch.randn(p.shape, generator=g).to(p.device)
+            if name.endswith("bias"):                                   # (nn.MultiheadAttention's in_proj_bias too)
+                p.copy_(0.3 * s * z)
+            elif name.endswith("weight") and p.dim() == 1:
+                p.copy_(1.0 + 0.4 * s * z)
+            elif name.endswith("weight") and p.dim() == 2:              # (in_proj_weight too)
+                p.mul_(1.0 + 0.3 * s * z.abs())
+            else:
+                p.add_(0.3 * s * z)
+
+
+def fold_tensors(model):
+    """the state-dict entries a weight image folds away (see trained_like_parameters): every bias and every LayerNorm gamma"""
+    return [k for k, v in model.state_dict().items() if k.endswith(".bias") or (k.endswith(".weight") and v.dim() == 1)]
+
+
+def zero_by_softmax_symmetry(name):
+    """key biases: a constant added to every logit of a softmax segment, so they cannot move any output"""
+    return name.endswith("lin_k.bias") or name.endswith("lin_k_node.bias") or name.endswith("lin_k_edge.bias")
+
+
 def maxdiff(a, b):
     return float((a.double() - b.double()).abs().max()) if a.numel() else 0.0
 
@@ -292,3 +363,42 @@ def oracle_grid_full_grads(model, cfg, batch_cpu, d_local=None, drop=None):
     finally:
         torch.set_default_dtype(torch.float32)
     return float(loss.detach()), {k: P[k].grad for k in names}
+
+
+def _isolated_batch(T):
+    """a scene whose lanes all lie beyond the radius and an ordinary one, then two single-actor scenes (no agent-agent edge into
+    them): targets of zero in-degree in the AA, AL and global attention next to targets with edges.  The single-actor scenes come
+    last: the reference numbers its fake agents by torch.unique over the agents that HAVE in-edges (ENC:90), so an agent without
+    any before an agent with some would hand that agent's in-edges to another fake agent"""
+    from trajsde_amd.data import collate
+    from trajsde_amd.synth import synth
+    far = synth(S=1, n=6, L=3, F=T, box=40.0, seed=72)
+    far["lane_actor_vectors"] = far["lane_actor_vectors"] + 1000.0
+    return collate([far, synth(S=1, n=7, L=4, F=T, box=50.0, seed=73), synth(S=1, n=1, L=2, F=T, box=30.0, seed=61),
+                    synth(S=1, n=1, L=2, F=T, box=30.0, seed=62)])
+
+
+def _cache_edge_batch(T):
+    """scenes of 32, 33, 256, 257 and 1 actors: the scene-cached global attention's chunk (32) and capacity (256) edges (the
+    single-actor scene last, see _isolated_batch)"""
+    from trajsde_amd.data import collate
+    from trajsde_amd.synth import synth
+    return collate([synth(S=1, n=n, L=6, F=T, box=box, seed=90 + i, mixed_source=i % 2 == 1)
+                    for i, (n, box) in enumerate(((32, 90.0), (33, 90.0), (256, 300.0), (257, 300.0), (1, 30.0)))])
+
+
+def _synth(**kw):
+    from trajsde_amd.synth import synth
+    return synth(**kw)
+
+
+# the batches the weights of trained_like_parameters are tested on: name -> (K, T, max_fut_t, batch maker)
+TRAINED_CASES = {
+    "mixed_k6_t20": (6, 20, 2.0, lambda: _synth(S=3, n=20, L=8, F=20, box=90.0, seed=9, mixed_source=True)),
+    "argo_dropout_k6_t30": (6, 30, 3.0, lambda: _synth(S=3, n=24, L=10, F=30, box=100.0, seed=21, source=1, history_dropout=0.4)),
+    "shipped_k10_t60": (10, 60, 6.0, lambda: _synth(S=2, n=18, L=8, F=60, box=100.0, seed=33, mixed_source=True)),
+    "isolated_k6_t20": (6, 20, 2.0, lambda: _isolated_batch(20)),
+    "cache_edges_k6_t20": (6, 20, 2.0, lambda: _cache_edge_batch(20)),
+}
+TRAINED_STRENGTHS = (1.0, 2.0)
+TRAINED_SEED = 11

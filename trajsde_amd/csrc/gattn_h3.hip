@@ -584,7 +584,9 @@ __global__ void k_scene_ptr(const int64_t* __restrict__ scene_of, int N, int A, 
   if (i < E && scene_of[esrc[i]] != scene_of[edst[i]]) scene_ptr[A + 1] = 1;
   if (i > N) return;
   const int64_t cur = i < N ? scene_of[i] : A, prev = i > 0 ? scene_of[i - 1] : -1;
-  if (cur < prev || cur > A || prev < -1) {
+  // a real node names a scene in [0, A): one that names scene A or beyond (a batch vector with more scenes than agent_index has
+  // entries) would lie outside every range and its aggregate row would never be written
+  if (cur < prev || (i < N ? (cur < 0 || cur >= A) : cur > A) || prev < -1) {
     scene_ptr[A + 1] = 1;
     return;
   }

@@ -161,7 +161,9 @@ class ParamTree(nn.Module):
         self.__dict__["_touched"] = self.__dict__.get("_touched", 0) + 1
 
     def version_stamp(self) -> int:
-        """Changes whenever any parameter is modified in place or re-assigned (optimizer step, load, .to()).
+        """Changes whenever any parameter is modified in place or re-assigned (optimizer step, load_state_dict, .to(), an in-place op
+        on the parameter under no_grad).  A write through `p.data` (or any other alias, such as a flat tensor the parameters are
+        views of) does NOT bump the parameter's `_version`: after one, call touch(), or the kernels keep the stale weight images.
         Called once per stage per forward, so it walks a cached list of (container dict, leaf name) slots instead of
         nn.Module.parameters() (0.2 ms of Python per call on this tree); the slots survive re-assignment of a leaf."""
         slots = self.__dict__.get("_stamp_slots")
