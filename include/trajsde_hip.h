@@ -74,7 +74,8 @@ typedef enum {
   TRAJSDE_STAGE_DECODER_MLP_BWD = 8, /* trajsde_mlp_decoder_l2_backward; num_layers = future steps */
   TRAJSDE_STAGE_ENCODER_GRID_BWD = 9, /* trajsde_encoder_grid_backward; num_layers = temporal layers */
   TRAJSDE_STAGE_DECODER_NLL_BWD = 10, /* trajsde_decoder_nll_backward: the DECODER_BWD table followed by the scale head (ABI 8) */
-  TRAJSDE_STAGE_DECODER_MILSTEIN = 11 /* trajsde_decoder_forward_milstein: the DECODER table; its blob + GFunc's transposes (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MILSTEIN = 11, /* trajsde_decoder_forward_milstein: the DECODER table; its blob + GFunc's transposes (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MLP_NLL_BWD = 12 /* trajsde_mlp_decoder_nll_backward: the DECODER_MLP_BWD table followed by the scale head (ABI 10) */
 } trajsde_stage;
 
 int trajsde_param_count(int stage, int num_layers /*aggregator*/, int num_modes);
@@ -341,6 +342,18 @@ int trajsde_mlp_decoder_l2_backward(int32_t N, int num_modes, int future_steps, 
                                     const uint8_t* reg_mask /*[N,T]*/, void* ws, int64_t ws_bytes, float* loss,
                                     int32_t* best_mode, float* const* grads, int n_grads, float* d_local, float* d_global,
                                     void* stream);
+
+/* The same under the Laplace negative log-likelihood (losses/laplace_nll_loss.py:18-47; ABI 10), like trajsde_decoder_nll_backward:
+ * the winner is the mode with the smallest masked L2, the loss is the mean over valid steps and both coordinates of
+ * log(2 s) + |y - l| / s with s = max(scale, eps), and the scale head (ELU + 1 + min_scale, dec_hivt_nusargo_grid.py:55-56) receives a
+ * gradient too.  `grads` follow trajsde_param_name(TRAJSDE_STAGE_DECODER_MLP_NLL_BWD, i): the DECODER_MLP_BWD table, then scale.0 / .1 / .3
+ * weight and bias; `blob_bwd` is that stage's image.  No valid step at all: loss 0 and zero gradients. */
+int64_t trajsde_mlp_decoder_nll_backward_ws_bytes(int32_t N);
+int trajsde_mlp_decoder_nll_backward(int32_t N, int num_modes, int future_steps, const float* blob_bwd, const float* local_embed,
+                                     const float* global_embed, const float* loc /*[K,N,T,4]*/, const float* y /*[N,T,2]*/,
+                                     const uint8_t* reg_mask /*[N,T]*/, float eps, float min_scale, void* ws, int64_t ws_bytes,
+                                     float* loss, int32_t* best_mode, float* const* grads, int n_grads, float* d_local,
+                                     float* d_global, void* stream);
 
 /* backward of the vanilla LocalEncoder: dL/d local_embed -> one gradient per parameter of
  * trajsde_param_name(TRAJSDE_STAGE_ENCODER_GRID_BWD, i) (buffers pre-zeroed by the caller); forward recomputed inside. */

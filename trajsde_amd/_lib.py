@@ -14,6 +14,7 @@ STAGE_ENCODER, STAGE_AGGREGATOR, STAGE_DECODER, STAGE_DECODER_BWD, STAGE_AGGREGA
 STAGE_ENCODER_GRID, STAGE_DECODER_MLP, STAGE_DECODER_MLP_BWD, STAGE_ENCODER_GRID_BWD = 6, 7, 8, 9
 STAGE_DECODER_NLL_BWD = 10
 STAGE_DECODER_MILSTEIN = 11   # trajsde_decoder_forward_milstein: the decoder blob + GFunc's transposed matrices (added at ABI 10)
+STAGE_DECODER_MLP_NLL_BWD = 12   # trajsde_mlp_decoder_nll_backward: the MLP decoder's L2 table + the scale head (added at ABI 10)
 
 
 ABI_VERSION = 10         # trajsde_graph grew aa_src / la_lane (2); trajsde_dropout arguments (3); training tapes (4);
@@ -134,6 +135,9 @@ SIGNATURES = {
     "trajsde_mlp_decoder_forward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, F32, P, I64, P, P, P]),
     "trajsde_mlp_decoder_backward_ws_bytes": (I64, [I32]),
     "trajsde_mlp_decoder_l2_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, P, P, I64, P, P, C.POINTER(P), C.c_int, P, P, P]),
+    "trajsde_mlp_decoder_nll_backward_ws_bytes": (I64, [I32]),
+    "trajsde_mlp_decoder_nll_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, P, F32, F32, P, I64, P, P, C.POINTER(P),
+                                                   C.c_int, P, P, P]),
     "trajsde_encoder_grid_backward_ws_bytes": (I64, [C.POINTER(Batch), C.POINTER(Graph), C.c_int]),
     "trajsde_encoder_grid_backward": (C.c_int, [C.POINTER(Batch), C.POINTER(Graph), P, P, P, C.c_int, C.c_int, P, P, I64, C.POINTER(P),
                                                 C.c_int, P]),

@@ -49,6 +49,16 @@ struct InitV { enum : int { DGAM = 0, DBET = 64, SIZE = 128 }; };               
 __global__ void k_l2_wta(const float* loc, const float* y, const uint8_t* mask, int N, int K, int T, int32_t* best, float* minsum,
                          int32_t* cnt, int KP);
 __global__ void k_l2_finalize(const float* minsum, const int32_t* cnt, int N, float* scal);
+// Laplace NLL (losses/laplace_nll_loss.py:29-44) of the winning mode: per-actor sums, then loss / (2 count) and 1 / (2 count)
+__global__ void k_nll_value(const float* loc, const float* y, const uint8_t* mask, const int32_t* best, int N, int T, float eps,
+                            float* minsum);
+__global__ void k_nll_finalize(const float* minsum, const int32_t* cnt, int N, float* scal);
+// what a head backward under the Laplace NLL reads of the forward: the winning mode's loc | scale values and the clamp
+struct NllArg {
+  const float* loc;        // [K, N, T, 4] forward outputs
+  const int32_t* best;     // winning mode per actor
+  float eps, min_scale;
+};
 __global__ void k_init_sel(const float* img, const float* local, const float* global, const int32_t* best, int N, float* y0, float* gsel);
 __global__ void k_dec_init_bwd(const float* img, const float* local, const float* gsel, const float* DY0, const int32_t* best, int N,
                                float* DA, float* d_local, float* d_global, float* vpart);

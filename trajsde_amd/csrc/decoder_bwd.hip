@@ -244,13 +244,9 @@ struct HeadV { enum : int { DGAM = 0, DBET = 64, DW3X = 128, DW3Y = 192, DB3 = 2
 
 // rows are (o, i): o = output step, i = actor.  S_in / DU / DS are [T][N][64]
 // MODE 0: the loc head under the winner-takes-all L2 loss.  MODE 1 / 2: the loc / the scale head under the Laplace NLL
-// (losses/laplace_nll_loss.py): `nll` carries the forward's outputs of the winning mode (the other head's value enters each
-// head's upstream gradient); the scale head's launch ADDS its state gradient to the loc head's (DS) and writes its own delta rows.
-struct NllArg {
-  const float* loc;        // [K, N, T, 4] forward outputs
-  const int32_t* best;     // winning mode per actor
-  float eps, min_scale;
-};
+// (losses/laplace_nll_loss.py): `nll` (bwd.hpp NllArg) carries the forward's outputs of the winning mode (the other head's value
+// enters each head's upstream gradient); the scale head's launch ADDS its state gradient to the loc head's (DS) and writes its own
+// delta rows.
 template <int MODE>
 __global__ __launch_bounds__(128) void k_head_bwd(const float* __restrict__ img, const float* __restrict__ states,
                                                   const float* __restrict__ out_tab, const float* __restrict__ y,

@@ -1,9 +1,11 @@
 // grid_bwd.hip -- backward of the vanilla HiVT variant's own pieces (SURVEY.md 8(f) rank 4 + rank 1): the MLPDecoder under
-// the winner-takes-all L2 loss and (below) the TemporalEncoder; the attention families and the node blocks reuse the
+// the winner-takes-all L2 loss or the Laplace NLL and (below) the TemporalEncoder; the attention families and the node blocks reuse the
 // kernels of encoder_bwd.hip / node_bwd.hip / aggregator_bwd.hip with 4 heads.
 //
-// MLPDecoder (GDEC:47-63) + L2 (losses/L2.py:10-27): only the winning mode of each actor carries gradient, so the head and
-// aggr_embed backward run on N rows.  The scale and pi heads get no gradient from this loss.
+// MLPDecoder (GDEC:47-63) + L2 (losses/L2.py:10-27) or the Laplace NLL (losses/laplace_nll_loss.py:18-47): only the winning mode
+// of each actor carries gradient, so the head and aggr_embed backward run on N rows.  Under L2 only the loc head is differentiated;
+// under the Laplace NLL the scale head too, in a launch of its own (two head images do not fit LDS together).  The pi head gets no
+// gradient from either loss.
 #include "attn_common.hpp"
 #include "bwd.hpp"
 #include "common.hpp"
@@ -15,14 +17,18 @@
 
 namespace tsde {
 
-// loc head forward + backward on the winning rows: out [N,64] -> l [2T]; dL/dl from (y, mask, 1/count).
-// writes H (relu output, input of loc.3), DL [N,128] (d l, zero beyond 2T), DU (d of loc.0's output), DOUT (d out);
-// per-wave (dgamma | dbeta) of loc.1 -> vpart[wave][128]
+// one head's forward + backward on the winning rows: out [N,64] -> l [2T]; dL/dl from (y, mask, 1/count).
+// writes H (relu output, input of .3), DL [N,128] (d l, zero beyond 2T), DU (d of .0's output), DOUT (d out);
+// per-wave (dgamma | dbeta) of .1 -> vpart[wave][128]
+// MODE 0: the loc head under the winner-takes-all L2 loss.  MODE 1 / 2: the loc / the scale head under the Laplace NLL; `nll`
+// carries the forward's loc | scale values of the winning mode (the other head's value enters each head's upstream gradient),
+// and the scale head's launch writes DOUT = DOUT_LOC + its own d out (loc first, then scale: one fixed order per element).
+template <int MODE>
 __global__ __launch_bounds__(256) void k_mlp_heads_bwd(const float* __restrict__ img, const float* __restrict__ out,
                                                        const float* __restrict__ y, const uint8_t* __restrict__ mask,
                                                        const float* __restrict__ scal, int N, int T, float* __restrict__ H,
                                                        float* __restrict__ DL, float* __restrict__ DU, float* __restrict__ DOUT,
-                                                       float* __restrict__ vpart) {
+                                                       float* __restrict__ vpart, NllArg nll, const float* __restrict__ DOUT_LOC) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   stage_blob(lds, img, MlpHeadBwdL::SIZE);
   using M = MlpHeadBwdL;
@@ -60,11 +66,33 @@ __global__ __launch_bounds__(256) void k_mlp_heads_bwd(const float* __restrict__
       for (int u2 = 0; u2 < 2; ++u2) {
         const int t = 8 * jt + 2 * L.g + u2;
         if (row < N && t < T && mask[int64_t(i) * T + t]) {
-          const float dx = l[jt][2 * u2] - y[(int64_t(i) * T + t) * 2], dy = l[jt][2 * u2 + 1] - y[(int64_t(i) * T + t) * 2 + 1];
-          const float nrm = sqrtf(dx * dx + dy * dy);
-          if (nrm > 0.f) {
-            dl[jt][2 * u2] = dx / nrm * inv_count;
-            dl[jt][2 * u2 + 1] = dy / nrm * inv_count;
+          if (MODE == 0) {
+            const float dx = l[jt][2 * u2] - y[(int64_t(i) * T + t) * 2], dy = l[jt][2 * u2 + 1] - y[(int64_t(i) * T + t) * 2 + 1];
+            const float nrm = sqrtf(dx * dx + dy * dy);
+            if (nrm > 0.f) {
+              dl[jt][2 * u2] = dx / nrm * inv_count;
+              dl[jt][2 * u2 + 1] = dy / nrm * inv_count;
+            }
+          } else {
+            const float yx = y[(int64_t(i) * T + t) * 2], yy = y[(int64_t(i) * T + t) * 2 + 1];
+            const float lx = l[jt][2 * u2], ly = l[jt][2 * u2 + 1];
+            const f4 fw = *reinterpret_cast<const f4*>(nll.loc + ((int64_t(nll.best[i]) * N + i) * T + t) * 4);
+            if (MODE == 1) {
+              // d/dl [ |y - l| / s ] = -sign(y - l) / s, s = max(scale, eps) of the forward (no gradient through the clamp's value)
+              const float sx = fmaxf(fw[2], nll.eps), sy = fmaxf(fw[3], nll.eps);
+              const float ex = yx - lx, ey = yy - ly;
+              dl[jt][2 * u2] = (ex > 0.f ? -1.f : ex < 0.f ? 1.f : 0.f) / sx * inv_count;
+              dl[jt][2 * u2 + 1] = (ey > 0.f ? -1.f : ey < 0.f ? 1.f : 0.f) / sy * inv_count;
+            } else {
+              // this head's outputs are the raw scales: s = ELU(raw) + 1 + min_scale (GDEC:55-56), clamped at eps in place, the gradient
+              // passing through (laplace_nll_loss.py:38-40); d/ds [ log 2s + |y - l| / s ] = 1/s - |y - l| / s^2
+              const float sxr = (lx > 0.f ? lx : fast_exp(lx) - 1.0f) + 1.0f + nll.min_scale;
+              const float syr = (ly > 0.f ? ly : fast_exp(ly) - 1.0f) + 1.0f + nll.min_scale;
+              const float sx = fmaxf(sxr, nll.eps), sy = fmaxf(syr, nll.eps);
+              const float ax = fabsf(yx - fw[0]), ay = fabsf(yy - fw[1]);
+              dl[jt][2 * u2] = (1.0f / sx - ax / (sx * sx)) * inv_count * (lx > 0.f ? 1.0f : fast_exp(lx));
+              dl[jt][2 * u2 + 1] = (1.0f / sy - ay / (sy * sy)) * inv_count * (ly > 0.f ? 1.0f : fast_exp(ly));
+            }
           }
         }
       }
@@ -81,6 +109,12 @@ __global__ __launch_bounds__(256) void k_mlp_heads_bwd(const float* __restrict__
     f4 dout[4];
     linear_t(dout, dh, lds + M::W0T, L);
     if (row < N) {
+      if (MODE == 2) {
+        f4 prev[4];
+        load_row(prev, DOUT_LOC, row, L.g);
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) dout[jt] = prev[jt] + dout[jt];
+      }
       store_row(h, H, row, L.g);
       store_row(dh, DU, row, L.g);
       store_row(dout, DOUT, row, L.g);
@@ -251,14 +285,16 @@ __global__ __launch_bounds__(1024) void k_tr_tok_grad(const float* __restrict__ 
 using namespace tsde;
 
 namespace {
-enum MlpGradSlot { L0W = 0, L0B, L1W, L1B, L3W, L3B, A0W, A0B, A1W, A1B, N_MLP_GRADS };
+// gradient slots, in the order of trajsde_param_name(TRAJSDE_STAGE_DECODER_MLP_BWD, i); the Laplace NLL stage
+// (TRAJSDE_STAGE_DECODER_MLP_NLL_BWD) appends the scale head's (pack.hip recipe_decoder_mlp_nll_bwd)
+enum MlpGradSlot { L0W = 0, L0B, L1W, L1B, L3W, L3B, A0W, A0B, A1W, A1B, N_MLP_GRADS, S0W = N_MLP_GRADS, S0B, S1W, S1B, S3W, S3B, N_MLP_GRADS_NLL };
 
 struct MlpBwdWs {
   int32_t *best, *cnt;
-  float *minsum, *scal, *out, *gsel, *H, *DL, *DU, *DOUT, *DA, *w3tmp, *b3tmp, *part, *cs, *vpart;
+  float *minsum, *scal, *out, *gsel, *H, *DL, *DU, *DOUT, *DA, *w3tmp, *b3tmp, *part, *cs, *vpart, *H2, *DL2, *DU2, *DOUT2;
   int64_t bytes, parts;
   bool ok;
-  MlpBwdWs(void* ws, int64_t n, int N) {
+  MlpBwdWs(void* ws, int64_t n, int N, bool nll = false) {
     Carver c(ws, n);
     const int64_t slab = int64_t(N) * 64;
     best = c.take<int32_t>(N); cnt = c.take<int32_t>(N); minsum = c.take<float>(N); scal = c.take<float>(4);
@@ -268,27 +304,38 @@ struct MlpBwdWs {
     parts = wgrad_max_parts(N, 1);
     part = c.take<float>(parts * 4096); cs = c.take<float>(parts * 64);
     vpart = c.take<float>(int64_t(512) * 4 * 128);
+    H2 = DL2 = DU2 = DOUT2 = nullptr;
+    if (nll) {                                               // the scale head's rows (Laplace NLL)
+      H2 = c.take<float>(slab); DL2 = c.take<float>(slab * 2); DU2 = c.take<float>(slab); DOUT2 = c.take<float>(slab);
+    }
     bytes = c.off + 256;
     ok = c.ok;
   }
 };
-}  // namespace
 
-extern "C" {
+// the .3 layer of a head [2T, 64]: two 64-row blocks into a 128-row scratch, the first 2T rows are the gradient
+int head3_wgrad(const WgradCtx& wc, const MlpBwdWs& w, const float* DL, const float* H, int N, int T, float* W3, float* B3) {
+  for (int b = 0; b < 2; ++b)
+    if (int rc = run_wgrad(wc, DL + 64 * b, 128, H, 64, N, N, w.w3tmp + b * MAT64, 64, 0, w.b3tmp + 64 * b, 0)) return rc;
+  TS_HIP(hipMemcpyAsync(W3, w.w3tmp, size_t(2 * T) * 64 * sizeof(float), hipMemcpyDeviceToDevice, wc.st));
+  TS_HIP(hipMemcpyAsync(B3, w.b3tmp, size_t(2 * T) * sizeof(float), hipMemcpyDeviceToDevice, wc.st));
+  return 0;
+}
 
-int64_t trajsde_mlp_decoder_backward_ws_bytes(int32_t N) { return MlpBwdWs(nullptr, 0, N).bytes; }
-
-int trajsde_mlp_decoder_l2_backward(int32_t N, int num_modes, int future_steps, const float* blob_bwd, const float* local_embed,
-                                    const float* global_embed, const float* loc, const float* y, const uint8_t* reg_mask, void* ws,
-                                    int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads, int n_grads,
-                                    float* d_local, float* d_global, void* stream_) {
+// shared body of trajsde_mlp_decoder_l2_backward / trajsde_mlp_decoder_nll_backward
+int mlp_decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N, int num_modes, int future_steps, const float* blob_bwd,
+                              const float* local_embed, const float* global_embed, const float* loc, const float* y,
+                              const uint8_t* reg_mask, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads,
+                              int n_grads, float* d_local, float* d_global, void* stream_) {
+  const char* who = nll ? "mlp_decoder_nll_backward" : "mlp_decoder_l2_backward";
   TS_REQUIRE(blob_bwd && local_embed && global_embed && loc && y && reg_mask && ws && loss && grads && d_local && d_global,
-             "mlp_decoder_l2_backward: null pointer");
-  TS_REQUIRE(N > 0 && num_modes > 0 && future_steps > 0 && future_steps <= 64, "mlp_decoder_l2_backward: need 0 < future_steps <= 64");
-  TS_REQUIRE(n_grads == N_MLP_GRADS, "mlp_decoder_l2_backward: gradient count does not match trajsde_param_count(DECODER_MLP_BWD)");
-  for (int i = 0; i < N_MLP_GRADS; ++i) TS_REQUIRE(grads[i] != nullptr, "mlp_decoder_l2_backward: null gradient buffer");
-  MlpBwdWs w(ws, ws_bytes, N);
-  if (!w.ok) return fail(TRAJSDE_ERR_WORKSPACE, "mlp_decoder_l2_backward: workspace too small");
+             std::string(who) + ": null pointer");
+  TS_REQUIRE(N > 0 && num_modes > 0 && future_steps > 0 && future_steps <= 64, std::string(who) + ": need 0 < future_steps <= 64");
+  const int want_grads = nll ? int(N_MLP_GRADS_NLL) : int(N_MLP_GRADS);
+  TS_REQUIRE(n_grads == want_grads, std::string(who) + ": gradient count does not match trajsde_param_count of the backward stage");
+  for (int i = 0; i < want_grads; ++i) TS_REQUIRE(grads[i] != nullptr, std::string(who) + ": null gradient buffer");
+  MlpBwdWs w(ws, ws_bytes, N, nll);
+  if (!w.ok) return fail(TRAJSDE_ERR_WORKSPACE, std::string(who) + ": workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const int K = num_modes, T = future_steps;
   const int ntiles = (N + 15) / 16;
@@ -298,30 +345,51 @@ int trajsde_mlp_decoder_l2_backward(int32_t N, int num_modes, int future_steps, 
     TS_REQUIRE(K >= 1 && K <= 256, "mlp decoder backward: 1 <= num_modes <= 256");
     int KP = 1;
     while (KP < K) KP <<= 1;
-    TS_LAUNCH(k_l2_wta, cdiv(N, 256 / KP), 256, 0, st, loc, y, reg_mask, N, K, T, w.best, w.minsum, w.cnt, KP);
+    TS_LAUNCH(k_l2_wta, cdiv(N, 256 / KP), 256, 0, st, loc, y, reg_mask, N, K, T, w.best, w.minsum, w.cnt, KP);   // the winner of both losses
   }
-  TS_LAUNCH(k_l2_finalize, 1, 1024, 0, st, w.minsum, w.cnt, N, w.scal);
+  if (nll) {
+    TS_LAUNCH(k_nll_value, cdiv(N, 256), 256, 0, st, loc, y, reg_mask, w.best, N, T, eps, w.minsum);
+    TS_LAUNCH(k_nll_finalize, 1, 1024, 0, st, w.minsum, w.cnt, N, w.scal);
+  } else {
+    TS_LAUNCH(k_l2_finalize, 1, 1024, 0, st, w.minsum, w.cnt, N, w.scal);
+  }
   TS_HIP(hipMemcpyAsync(loss, w.scal, sizeof(float), hipMemcpyDeviceToDevice, st));
   if (best_mode) TS_HIP(hipMemcpyAsync(best_mode, w.best, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st));
   const int g128 = vec_grid(ntiles, 128, InitBwdL::SIZE * 4);
   TS_LAUNCH(k_init_sel, g128, 128, InitBwdL::AE_END * 4, st, init_img, local_embed, global_embed, w.best, N, w.out, w.gsel);
   const int gh = vec_grid(ntiles, 256, MlpHeadBwdL::SIZE * 4);
-  TS_LAUNCH(k_mlp_heads_bwd, gh, 256, MlpHeadBwdL::SIZE * 4, st, blob_bwd + MlpDecBwdBlob::HEAD, w.out, y, reg_mask, w.scal, N, T, w.H, w.DL,
-            w.DU, w.DOUT, w.vpart);
+  const NllArg na{loc, w.best, eps, min_scale};
+  if (nll)
+    TS_LAUNCH(k_mlp_heads_bwd<1>, gh, 256, MlpHeadBwdL::SIZE * 4, st, blob_bwd + MlpDecBwdBlob::HEAD, w.out, y, reg_mask, w.scal, N, T, w.H,
+              w.DL, w.DU, w.DOUT, w.vpart, na, nullptr);
+  else
+    TS_LAUNCH(k_mlp_heads_bwd<0>, gh, 256, MlpHeadBwdL::SIZE * 4, st, blob_bwd + MlpDecBwdBlob::HEAD, w.out, y, reg_mask, w.scal, N, T, w.H,
+              w.DL, w.DU, w.DOUT, w.vpart, na, nullptr);
   {
     ColsumBatch cb(st, gh * 4, 128);
     cb.add(w.vpart, 64, grads[L1W]);
     cb.add(w.vpart + 64, 64, grads[L1B]);
     if (int rc = cb.flush()) return rc;
   }
-  // loc.3 [2T, 64]: two 64-row blocks into a 128-row scratch, the first 2T rows are the gradient
-  for (int b = 0; b < 2; ++b)
-    if (int rc = run_wgrad(wc, w.DL + 64 * b, 128, w.H, 64, N, N, w.w3tmp + b * MAT64, 64, 0, w.b3tmp + 64 * b, 0)) return rc;
-  TS_HIP(hipMemcpyAsync(grads[L3W], w.w3tmp, size_t(2 * T) * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  TS_HIP(hipMemcpyAsync(grads[L3B], w.b3tmp, size_t(2 * T) * sizeof(float), hipMemcpyDeviceToDevice, st));
+  // the scale head (its image follows the L2 blob: MlpDecNllBwdBlob): own rows; its d out = the loc head's + its own
+  const float* dout = w.DOUT;
+  if (nll) {
+    TS_LAUNCH(k_mlp_heads_bwd<2>, gh, 256, MlpHeadBwdL::SIZE * 4, st, blob_bwd + MlpDecNllBwdBlob::HEAD_SC, w.out, y, reg_mask, w.scal, N, T,
+              w.H2, w.DL2, w.DU2, w.DOUT2, w.vpart, na, w.DOUT);
+    ColsumBatch cb(st, gh * 4, 128);
+    cb.add(w.vpart, 64, grads[S1W]);
+    cb.add(w.vpart + 64, 64, grads[S1B]);
+    if (int rc = cb.flush()) return rc;
+    dout = w.DOUT2;
+  }
+  if (int rc = head3_wgrad(wc, w, w.DL, w.H, N, T, grads[L3W], grads[L3B])) return rc;
   if (int rc = run_wgrad(wc, w.DU, 64, w.out, 64, N, N, grads[L0W], 64, 0, grads[L0B], 0)) return rc;
+  if (nll) {
+    if (int rc = head3_wgrad(wc, w, w.DL2, w.H2, N, T, grads[S3W], grads[S3B])) return rc;
+    if (int rc = run_wgrad(wc, w.DU2, 64, w.out, 64, N, N, grads[S0W], 64, 0, grads[S0B], 0)) return rc;
+  }
   TS_HIP(hipMemsetAsync(d_global, 0, size_t(K) * N * 64 * sizeof(float), st));
-  TS_LAUNCH(k_dec_init_bwd, g128, 128, InitBwdL::SIZE * 4, st, init_img, local_embed, w.gsel, w.DOUT, w.best, N, w.DA, d_local, d_global,
+  TS_LAUNCH(k_dec_init_bwd, g128, 128, InitBwdL::SIZE * 4, st, init_img, local_embed, w.gsel, dout, w.best, N, w.DA, d_local, d_global,
             w.vpart);
   {
     ColsumBatch cb(st, g128 * 2, InitV::SIZE);
@@ -331,6 +399,30 @@ int trajsde_mlp_decoder_l2_backward(int32_t N, int num_modes, int future_steps, 
   }
   if (int rc = run_wgrad(wc, w.DA, 64, w.gsel, 64, N, N, grads[A0W], 128, 0, grads[A0B], 0)) return rc;      // cat(global, local)
   return run_wgrad(wc, w.DA, 64, local_embed, 64, N, N, grads[A0W], 128, 64, nullptr, 0);
+}
+}  // namespace
+
+extern "C" {
+
+int64_t trajsde_mlp_decoder_backward_ws_bytes(int32_t N) { return MlpBwdWs(nullptr, 0, N).bytes; }
+
+int64_t trajsde_mlp_decoder_nll_backward_ws_bytes(int32_t N) { return MlpBwdWs(nullptr, 0, N, true).bytes; }
+
+int trajsde_mlp_decoder_l2_backward(int32_t N, int num_modes, int future_steps, const float* blob_bwd, const float* local_embed,
+                                    const float* global_embed, const float* loc, const float* y, const uint8_t* reg_mask, void* ws,
+                                    int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads, int n_grads,
+                                    float* d_local, float* d_global, void* stream_) {
+  return mlp_decoder_backward_impl(false, 0.f, 0.f, N, num_modes, future_steps, blob_bwd, local_embed, global_embed, loc, y, reg_mask, ws,
+                                   ws_bytes, loss, best_mode, grads, n_grads, d_local, d_global, stream_);
+}
+
+int trajsde_mlp_decoder_nll_backward(int32_t N, int num_modes, int future_steps, const float* blob_bwd, const float* local_embed,
+                                     const float* global_embed, const float* loc, const float* y, const uint8_t* reg_mask, float eps,
+                                     float min_scale, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads,
+                                     int n_grads, float* d_local, float* d_global, void* stream_) {
+  TS_REQUIRE(eps > 0.f, "mlp_decoder_nll_backward: eps must be positive");
+  return mlp_decoder_backward_impl(true, eps, min_scale, N, num_modes, future_steps, blob_bwd, local_embed, global_embed, loc, y, reg_mask,
+                                   ws, ws_bytes, loss, best_mode, grads, n_grads, d_local, d_global, stream_);
 }
 
 }  // extern "C"

@@ -523,6 +523,10 @@ struct EncGridBwdBlob {   // EncBwdBlob's AA / AL images at their offsets (recur
 struct MlpDecBwdBlob {
   enum : int { HEAD = 0, INIT = MlpHeadBwdL::SIZE, SIZE = INIT + InitBwdL::SIZE };
 };
+struct MlpDecNllBwdBlob {   // Laplace NLL: the L2 blob followed by the scale head's image (a launch of its own: two do not fit LDS)
+  enum : int { HEAD_SC = MlpDecBwdBlob::SIZE, SIZE = HEAD_SC + MlpHeadBwdL::SIZE };
+};
+static_assert(MlpHeadBwdL::SIZE * 4 <= 160 * 1024 && MlpDecNllBwdBlob::HEAD_SC % 4 == 0, "MLP head backward image: fits LDS, 16-byte aligned");
 static_assert(SweepL::SIZE * 4 <= 160 * 1024, "sweep image must fit LDS");
 static_assert(DecBwdBlob::HEAD % 4 == 0 && DecBwdBlob::INIT % 4 == 0, "16-byte aligned images");
 

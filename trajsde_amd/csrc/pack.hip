@@ -876,17 +876,25 @@ static void recipe_aggr_embed_bwd(Packer& P, int b) {      // aggr_embed of eith
   P.matT("aggr_embed.0.weight", b + I::WA_GT, 128, 0);
   P.matT("aggr_embed.0.weight", b + I::WA_LT, 128, 64);
 }
+// one head of the MLP decoder (`p` = loc | scale) as a MlpHeadBwdL image at `h`
+static void recipe_mlp_head_bwd(Packer& P, const std::string& p, int h, int T) {
+  using H = MlpHeadBwdL;
+  P.lin(p + ".0", h + H::W0, h + H::B0);
+  P.ln(p + ".1", h + H::G, h + H::E);
+  P.mat_pad(p + ".3.weight", h + H::W3, 8, 4, 64, 2 * T);
+  P.vec(p + ".3.bias", h + H::B3, 2 * T);
+  P.matT(p + ".3.weight", h + H::W3T, 64, 0, 4, 8, 2 * T);          // (W3 [2T,64])^T as a 64 x 128 image
+  P.matT(p + ".0.weight", h + H::W0T, 64);
+}
 // MLPDecoder backward (L2 on loc): loc head + aggr_embed; `scale` and `pi` get no gradient from that loss
 static void recipe_decoder_mlp_bwd(Packer& P, int T) {
-  using H = MlpHeadBwdL;
-  const int h = MlpDecBwdBlob::HEAD;
-  P.lin("loc.0", h + H::W0, h + H::B0);
-  P.ln("loc.1", h + H::G, h + H::E);
-  P.mat_pad("loc.3.weight", h + H::W3, 8, 4, 64, 2 * T);
-  P.vec("loc.3.bias", h + H::B3, 2 * T);
-  P.matT("loc.3.weight", h + H::W3T, 64, 0, 4, 8, 2 * T);          // (W3 [2T,64])^T as a 64 x 128 image
-  P.matT("loc.0.weight", h + H::W0T, 64);
+  recipe_mlp_head_bwd(P, "loc", MlpDecBwdBlob::HEAD, T);
   recipe_aggr_embed_bwd(P, MlpDecBwdBlob::INIT);
+}
+// Laplace NLL: the L2 table and images, then the scale head's (its gradient slots follow the L2 ones); `pi` gets no gradient
+static void recipe_decoder_mlp_nll_bwd(Packer& P, int T) {
+  recipe_decoder_mlp_bwd(P, T);
+  recipe_mlp_head_bwd(P, "scale", MlpDecNllBwdBlob::HEAD_SC, T);
 }
 
 // backward images of the decoder stage (loc head, drift/diffusion nets, aggr_embed); `pi` and `scale` receive no
@@ -1082,6 +1090,7 @@ static bool run_recipe(Packer& P, int stage, int nl, int K) {
     case TRAJSDE_STAGE_ENCODER_GRID: recipe_encoder_grid(P, nl); return true;
     case TRAJSDE_STAGE_DECODER_MLP: recipe_decoder_mlp(P, nl); return true;
     case TRAJSDE_STAGE_DECODER_MLP_BWD: recipe_decoder_mlp_bwd(P, nl); return true;
+    case TRAJSDE_STAGE_DECODER_MLP_NLL_BWD: recipe_decoder_mlp_nll_bwd(P, nl); return true;
     case TRAJSDE_STAGE_ENCODER_GRID_BWD: recipe_encoder_grid_bwd(P, nl); return true;
   }
   return false;
@@ -1216,6 +1225,7 @@ int64_t trajsde_blob_floats(int stage, int num_layers, int num_modes) {
     case TRAJSDE_STAGE_ENCODER_GRID: return EncGridBlob::size(num_layers);
     case TRAJSDE_STAGE_DECODER_MLP: return MlpDecBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_MLP_BWD: return MlpDecBwdBlob::SIZE;
+    case TRAJSDE_STAGE_DECODER_MLP_NLL_BWD: return MlpDecNllBwdBlob::SIZE;
     case TRAJSDE_STAGE_ENCODER_GRID_BWD: return EncGridBwdBlob::size(num_layers);
   }
   return fail(TRAJSDE_ERR_INVALID, "unknown stage");

@@ -40,7 +40,8 @@ class LaplaceNLLLoss:
     """losses/laplace_nll_loss.py:18-47: Laplace negative log-likelihood of the winner-takes-all mode (the mode with the
     smallest masked mean L2), scale clamped at `eps`.  No shipped configuration names it (CFG:78-83 use L2 + DiffBCE), so
     this class gives its VALUE on the forward's device tensors; `training_step` differentiates it through
-    trajsde_decoder_nll_backward (the scale head is trained under it, unlike under L2)."""
+    trajsde_decoder_nll_backward, or trajsde_mlp_decoder_nll_backward in the vanilla variant (the scale head is trained under it,
+    unlike under L2)."""
 
     def __init__(self, eps: float = 1e-6, reduction: str = "mean") -> None:
         if reduction != "mean":

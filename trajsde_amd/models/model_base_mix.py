@@ -2,8 +2,9 @@
 same YAML registry, `forward(data) -> dict`, the same in-place side effects on `data` (rotate_mat, rotated y) and the
 same validation / test step bookkeeping as the SDE model; the stages are the HIP-backed LocalEncoder,
 GlobalInteractor and MLPDecoder.  Deterministic (no SDE noise).  `training_step` differentiates the shipped loss of
-this configuration (L2, configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml:62-66) through the HIP backward entry points
-(trajsde_mlp_decoder_l2_backward -> trajsde_aggregator_backward_heads -> trajsde_encoder_grid_backward); the `ts_drop`
+this configuration (L2, configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml:62-66) or the Laplace NLL (losses/laplace_nll_loss.py,
+under which the decoder's scale head is trained too) through the HIP backward entry points (trajsde_mlp_decoder_l2_backward or
+trajsde_mlp_decoder_nll_backward -> trajsde_aggregator_backward_heads -> trajsde_encoder_grid_backward); the `ts_drop`
 augmentation (models/model_base_mix.py:95-100) masks history steps of the batch before the forward, as there.  The YAML's
 `nodecay` flag is stored and, as in the reference (no code reads it), has no effect: AdamW runs over all parameters.
 """
@@ -19,14 +20,18 @@ from trajsde_amd.models.model_base_mix_sde import resolve_class
 
 
 class _GridPathLoss(torch.autograd.Function):
-    """w * L2 as one autograd node over the parameters (see model_base_mix_sde._PathLoss)"""
+    """w * (L2 or LaplaceNLLLoss) as one autograd node over the parameters (see model_base_mix_sde._PathLoss)"""
 
     @staticmethod
     def forward(ctx, model, data, noise, w_l2, *params):
         with torch.no_grad():
             out = model(data, noise=noise)
             local, glob = out["local_embed"], out["global_embed"]
-            dec = model.decoder._rt.mlp_decoder_l2_backward(data, local, glob, out)
+            reg, eps = model._regression_loss()
+            if reg == "LaplaceNLLLoss":
+                dec = model.decoder._rt.mlp_decoder_nll_backward(data, local, glob, out, eps=eps)
+            else:
+                dec = model.decoder._rt.mlp_decoder_l2_backward(data, local, glob, out)
             agg = model.aggregator._rt.aggregator_backward(data, local, dec["d_global_embed"], noise)
             enc = model.encoder._rt.encoder_grid_backward(data, dec["d_local_embed"] + agg["d_local_embed"], noise)
             by_name = {"decoder." + n: g for n, g in dec["grads"].items()}
@@ -35,7 +40,7 @@ class _GridPathLoss(torch.autograd.Function):
             ctx.grads = [by_name.get(n) for n in model._param_names]
             ctx.w = w_l2
             model.last_output = out
-            model.last_losses = {"L2": dec["loss"].detach()}
+            model.last_losses = {reg: dec["loss"].detach()}
             return (w_l2 * dec["loss"]).clone()
 
     @staticmethod
@@ -109,11 +114,22 @@ class PredictionModel(LightningHooks):
         runtime.prefetch_graph(data, float(enc.local_radius), int(enc.historical_steps), runtime.NoiseSpec(seed=0), fake_agents=False,
                                main_stream=main_stream)
 
+    def _regression_loss(self):
+        """(name, eps) of the configured regression loss: "L2" (the shipped one) or "LaplaceNLLLoss" (losses/laplace_nll_loss.py:
+        the scale head is trained as well)"""
+        for name, fn in zip(self.loss_names, self.losses):
+            if name == "LaplaceNLLLoss":
+                return name, float(getattr(fn, "eps", 1e-6))
+        return "L2", None
+
     def params_with_gradient(self):
+        """the parameters the configured loss reaches: everything but the decoder's pi head, and its scale head under L2 (the
+        reference's autograd leaves their `.grad` at None, so AdamW skips them)"""
         from trajsde_amd import _lib
         reached = set()
+        dec_stage = _lib.STAGE_DECODER_MLP_NLL_BWD if self._regression_loss()[0] == "LaplaceNLLLoss" else _lib.STAGE_DECODER_MLP_BWD
         for stage, sid in (("encoder", _lib.STAGE_ENCODER_GRID_BWD), ("aggregator", _lib.STAGE_AGGREGATOR_BWD),
-                           ("decoder", _lib.STAGE_DECODER_MLP_BWD)):
+                           ("decoder", dec_stage)):
             reached |= {f"{stage}.{n}" for n in getattr(self, stage)._rt.param_names(sid)}
         return [p for n, p in self.named_parameters() if n in reached]
 
@@ -130,13 +146,15 @@ class PredictionModel(LightningHooks):
         data.padding_mask[:, :h] = data.padding_mask[:, :h] | mask
 
     def training_step(self, data, batch_idx, noise=None):
-        """models/model_base_mix.py:94-114 for the shipped loss (L2).  In train mode the stages' `dropout` (0.1 in the reference's YAML) is
-        applied at the reference's 36 sites -- the four of every attention block and of every TemporalEncoder layer -- with masks cut
-        from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()` switches it off."""
+        """models/model_base_mix.py:94-114 for ONE regression loss: the shipped L2, or LaplaceNLLLoss (losses/laplace_nll_loss.py).  In
+        train mode the stages' `dropout` (0.1 in the reference's YAML) is applied at the reference's 36 sites -- the four of every attention
+        block and of every TemporalEncoder layer -- with masks cut from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()`
+        switches it off."""
+        if self.loss_names not in (["L2"], ["LaplaceNLLLoss"]):
+            raise NotImplementedError("training_step differentiates ONE regression loss (L2 or LaplaceNLLLoss) through the HIP kernels; "
+                                      f"configured: {self.loss_names}")
         if getattr(self, "ts_drop", False):
             self.apply_ts_drop(data)
-        if self.loss_names != ["L2"]:
-            raise NotImplementedError(f"training_step differentiates L2 through the HIP kernels; configured: {self.loss_names}")
         if not getattr(self.decoder, "uncertain", True):      # (losses/L2.py:12 chunks loc | scale out of four channels: see the SDE model)
             raise NotImplementedError("training with `uncertain: False` is not built: the reference's L2 regresses x against both targets "
                                       "on a two-channel output (losses/L2.py:12)")
@@ -147,7 +165,8 @@ class PredictionModel(LightningHooks):
             self._param_names = [n for n, _ in self.named_parameters()]
         params = [p for _, p in self.named_parameters()]
         loss = _GridPathLoss.apply(self, data, noise, float(self.loss_weights[0]), *params)
-        self.log_value("train/L2", self.last_losses["L2"], prog_bar=True, on_step=True, on_epoch=True,
+        name = self.loss_names[0]
+        self.log_value(f"train/{name}", self.last_losses[name], prog_bar=True, on_step=True, on_epoch=True,
                        batch_size=int(self.last_output["loc"].size(1)))          # models/model_base_mix.py:112
         lr = self.current_lr()
         if lr is not None:

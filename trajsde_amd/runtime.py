@@ -1059,7 +1059,22 @@ class StageRuntime:
     def mlp_decoder_l2_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor,
                                 out: Dict[str, torch.Tensor]) -> Dict[str, object]:
         """L2 (winner takes all) on `out` = mlp_decoder_forward(...) and its gradients, like decoder_l2_backward"""
+        return self._mlp_decoder_backward(data, local_embed, global_embed, out, nll_eps=None)
+
+    def mlp_decoder_nll_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor,
+                                 out: Dict[str, torch.Tensor], eps: float = 1e-6) -> Dict[str, object]:
+        """Laplace negative log-likelihood of the winning mode (losses/laplace_nll_loss.py:18-47) on `out` = mlp_decoder_forward(...)
+        and its gradients -- like mlp_decoder_l2_backward, with the scale head differentiated as well (grads keyed by
+        param_names(STAGE_DECODER_MLP_NLL_BWD)); `pi.*` gets no gradient"""
+        return self._mlp_decoder_backward(data, local_embed, global_embed, out, nll_eps=float(eps))
+
+    def _mlp_decoder_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
+                              nll_eps: Optional[float]) -> Dict[str, object]:
+        """shared body of mlp_decoder_l2_backward / mlp_decoder_nll_backward (`nll_eps` None: L2)"""
         m = self.module
+        if nll_eps is not None and not getattr(m, "uncertain", True):
+            raise _lib.TrajsdeError("LaplaceNLLLoss needs the decoder's scale head: `uncertain: False` has none "
+                                    "(dec_hivt_nusargo_grid.py:31, losses/laplace_nll_loss.py:28 chunks loc | scale out of four channels)")
         dev = local_embed.device
         K, T, N = int(m.num_modes), int(m.future_steps), local_embed.shape[0]
         y = data["y"]
@@ -1068,21 +1083,27 @@ class StageRuntime:
         y = y.to(torch.float32).contiguous()
         mask = out["reg_mask"].contiguous().view(torch.uint8)
         L = _lib.lib()
-        names = self.param_names(_lib.STAGE_DECODER_MLP_BWD)
-        grads = self._grad_buffers(_lib.STAGE_DECODER_MLP_BWD)
+        stage = _lib.STAGE_DECODER_MLP_BWD if nll_eps is None else _lib.STAGE_DECODER_MLP_NLL_BWD
+        names = self.param_names(stage)
+        grads = self._grad_buffers(stage)
         arr, _keep = grads.pointer_array()
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         best = torch.empty(N, device=dev, dtype=torch.int32)
         d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
         d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
-        ws_bytes = L.trajsde_mlp_decoder_backward_ws_bytes(N)
-        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         with torch.cuda.device(dev):
-            _lib.check(L.trajsde_mlp_decoder_l2_backward(
-                N, K, T, self.blob(_lib.STAGE_DECODER_MLP_BWD).data_ptr(), local_embed.contiguous().data_ptr(),
-                global_embed.contiguous().data_ptr(), _loc4(out).data_ptr(), y.data_ptr(), mask.data_ptr(), ws.data_ptr(),
-                ws_bytes, loss.data_ptr(), best.data_ptr(), arr, len(names), d_local.data_ptr(), d_global.data_ptr(), _stream()),
-                "trajsde_mlp_decoder_l2_backward")
+            head = (N, K, T, self.blob(stage).data_ptr(), local_embed.contiguous().data_ptr(), global_embed.contiguous().data_ptr(),
+                    _loc4(out).data_ptr(), y.data_ptr(), mask.data_ptr())
+            tail = (loss.data_ptr(), best.data_ptr(), arr, len(names), d_local.data_ptr(), d_global.data_ptr(), _stream())
+            if nll_eps is None:
+                ws_bytes = L.trajsde_mlp_decoder_backward_ws_bytes(N)
+                ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+                _lib.check(L.trajsde_mlp_decoder_l2_backward(*head, ws.data_ptr(), ws_bytes, *tail), "trajsde_mlp_decoder_l2_backward")
+            else:
+                ws_bytes = L.trajsde_mlp_decoder_nll_backward_ws_bytes(N)
+                ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+                _lib.check(L.trajsde_mlp_decoder_nll_backward(*head, float(nll_eps), float(m.min_scale), ws.data_ptr(), ws_bytes, *tail),
+                           "trajsde_mlp_decoder_nll_backward")
         return {"loss": loss[0], "best_mode": best, "grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
 
 
