@@ -189,8 +189,8 @@ def reference_laplace_nll(y, out_loc4, reg_mask, eps=1e-6):
     return nll[reg_mask].mean(), best
 
 
-def oracle_full_grads(model, cfg, batch_cpu, seed, w_l2, w_diff, want_parts=False, drop=None, nll_eps=None):
-    """end-to-end autograd over the oracle (float64): encoder -> aggregator -> decoder -> w_l2 L2 (or, with `nll_eps`, the
+def oracle_full_grads(model, cfg, batch_cpu, seed, w_l2, w_diff, want_parts=False, drop=None, nll_eps=None, dt=torch.float64):
+    """end-to-end autograd over the oracle (float64, or `dt`): encoder -> aggregator -> decoder -> w_l2 L2 (or, with `nll_eps`, the
     Laplace NLL) + w_diff DiffBCE;
     `drop`: a restate.PhiloxDropout for train-mode dropout (the masks the HIP kernels cut from their Philox stream)"""
     import restate
@@ -199,7 +199,6 @@ def oracle_full_grads(model, cfg, batch_cpu, seed, w_l2, w_diff, want_parts=Fals
     c = restate.flat_cfg(cfg)
     es = encoder_schedule(c["historical_steps"], c["max_past_t"], c["minimum_step"])
     ds = decoder_schedule(c["future_steps"], c["max_fut_t"], c["min_stepsize"])
-    dt = torch.float64
     P = {k: (v.detach().cpu().to(dt) if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
     names = [k for k in P if P[k].is_floating_point()]
     for k in names:
@@ -402,3 +401,174 @@ TRAINED_CASES = {
 }
 TRAINED_STRENGTHS = (1.0, 2.0)
 TRAINED_SEED = 11
+
+# ----------------------------------------------------------------------------- backward: per-stage oracles and the comparison rule
+BACKWARD_REL = 2e-4             # the backward tests' bound: of each gradient tensor's largest entry
+KEY_BIAS_ABS = 5e-5             # key biases: zero in exact arithmetic, an absolute bound on both sides
+
+
+class NoiseAs:
+    """a restate noise source whose float32 normals are handed on in `dt` (Float64Noise for any dtype)"""
+
+    def __init__(self, inner, dt):
+        self.inner, self.dt = inner, dt
+
+    def fake_agent(self, shape):
+        return self.inner.fake_agent(shape).detach().cpu().to(self.dt)
+
+    def encoder(self, idx, shape):
+        return self.inner.encoder(idx, shape).detach().cpu().to(self.dt)
+
+    def decoder(self, k, shape):
+        return self.inner.decoder(k, shape).detach().cpu().to(self.dt)
+
+
+def params_as(model, dt, prefix):
+    """(P in `dt`, the names under `prefix` that require grad)"""
+    P = {k: (v.detach().cpu().to(dt) if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
+    names = [k for k in P if k.startswith(prefix) and P[k].is_floating_point() and not k.endswith("attn_mask")]
+    for k in names:
+        P[k].requires_grad_(True)
+    return P, names
+
+
+def batch_as(batch_cpu, dt):
+    b = clone_batch(batch_cpu).to("cpu")
+    for k in b.keys:
+        if torch.is_tensor(b[k]) and b[k].is_floating_point():
+            b[k] = b[k].to(dt)
+    return b
+
+
+def stage_grads(P, names, prefix):
+    return {k[len(prefix):]: (P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])) for k in names}
+
+
+def oracle_decoder_grads(model, cfg, batch_cpu, local, glob, y_rot, seed, nll_eps=None, dt=torch.float64):
+    """autograd over the oracle's SDE decoder in `dt` on the given (fp32) embeddings and the fp32 Philox normals of `seed`, under the
+    L2 loss (or, with `nll_eps`, the Laplace NLL) -> (loss, best mode, {decoder param: grad}, d local_embed, d global_embed)"""
+    import restate
+    from trajsde_amd.schedule import decoder_schedule
+    c = restate.flat_cfg(cfg)
+    P, names = params_as(model, dt, "decoder.")
+    lo = local.detach().cpu().to(dt).requires_grad_(True)
+    gl = glob.detach().cpu().to(dt).requires_grad_(True)
+    sched = decoder_schedule(c["future_steps"], c["max_fut_t"], c["min_stepsize"])
+    torch.set_default_dtype(dt)
+    try:
+        with torch.enable_grad():
+            out = restate.sde_decoder(P, c, batch_as(batch_cpu, dt), lo, gl, NoiseAs(restate.PhiloxNoise(seed), dt), sched)
+            yr = y_rot.detach().cpu().to(dt)
+            if nll_eps is None:
+                loss, best = reference_l2(yr, out["loc"][..., :2], out["reg_mask"])
+            else:
+                loss, best = reference_laplace_nll(yr, out["loc"], out["reg_mask"], nll_eps)
+            loss.backward()
+    finally:
+        torch.set_default_dtype(torch.float32)
+    return float(loss.detach()), best, stage_grads(P, names, "decoder."), lo.grad, gl.grad
+
+
+def oracle_aggregator_grads(model, cfg, batch_cpu, local, d_glob, heads=8, dt=torch.float64):
+    """autograd over the oracle's global interactor in `dt` under sum(global_embed * d_glob) -> ({aggregator param: grad}, d local)"""
+    import restate
+    c = dict(restate.flat_cfg(cfg), num_heads=heads)
+    P, names = params_as(model, dt, "aggregator.")
+    lo = local.detach().cpu().to(dt).requires_grad_(True)
+    b = batch_as(batch_cpu, dt)
+    torch.set_default_dtype(dt)
+    try:
+        rot, _ = restate.rotate_inputs(b)
+        with torch.enable_grad():
+            glob = restate.global_interactor(P, c, b, rot, lo)
+            (glob * d_glob.detach().cpu().to(dt)).sum().backward()
+    finally:
+        torch.set_default_dtype(torch.float32)
+    return stage_grads(P, names, "aggregator."), lo.grad
+
+
+def oracle_encoder_grads(model, cfg, batch_cpu, d_local, seed, diff_weight, dt=torch.float64):
+    """autograd over the oracle's SDE local encoder in `dt` under sum(local_embed * d_local) + diff_weight * DiffBCE
+    -> ({encoder param: grad}, DiffBCE, d aa_out)"""
+    import restate
+    import torch.nn.functional as F
+    from trajsde_amd.schedule import encoder_schedule
+    c = restate.flat_cfg(cfg)
+    sched = encoder_schedule(c["historical_steps"], c["max_past_t"], c["minimum_step"])
+    P, names = params_as(model, dt, "encoder.")
+    b = batch_as(batch_cpu, dt)
+    torch.set_default_dtype(dt)
+    try:
+        rot, _ = restate.rotate_inputs(b)
+        with torch.enable_grad():
+            local, diff_in, diff_out, inter = restate.local_encoder(P, c, b, rot, NoiseAs(restate.PhiloxNoise(seed), dt), sched, True)
+            inter["aa_out"].retain_grad()
+            bce = (F.binary_cross_entropy(diff_in, torch.zeros_like(diff_in)) +
+                   F.binary_cross_entropy(diff_out, torch.ones_like(diff_out)))
+            ((local * d_local.detach().cpu().to(dt)).sum() + diff_weight * bce).backward()
+    finally:
+        torch.set_default_dtype(torch.float32)
+    return stage_grads(P, names, "encoder."), float(bce.detach()), inter["aa_out"].grad
+
+
+def deviation(a, b):
+    """{name: max|a - b|} over the names of `b` (a float32 oracle's own deviation from the float64 one)"""
+    return {k: (maxdiff(a[k], w) if w is not None and a.get(k) is not None else 0.0) for k, w in b.items()}
+
+
+def compare_grads(tag, got, want, noise32=None, rel=BACKWARD_REL):
+    """the backward tests' per-tensor rule over `got` {name: tensor} against `want` {name: float64 tensor, or None for no gradient
+    path (then zero is wanted)}: err = max|got - want| <= rel * max|want| + 1e-7; key biases (zero_by_softmax_symmetry) get
+    KEY_BIAS_ABS on both err and max|want|.  `noise32` {name: the float32 oracle's deviation from float64} widens a tensor's bound to
+    2 x that deviation where it is larger (the ill-conditioned encoder gradients, test_encoder_backward_matches_autograd) -- nothing
+    else does.  Prints the worst error relative to its tensor's max ("[trained-backward] <tag>: ...") and returns the offenders."""
+    bad, worst = [], (0.0, "-", 0.0)
+    for k in sorted(got):
+        g = got[k].detach().cpu().double()
+        w = want.get(k)
+        w = torch.zeros_like(g) if w is None else w.detach().cpu().double()
+        if g.shape != w.shape or not bool(torch.isfinite(g).all()):
+            bad.append((k, "shape or non-finite", tuple(g.shape), tuple(w.shape)))
+            continue
+        scale = float(w.abs().max()) if w.numel() else 0.0
+        err = float((g - w).abs().max()) if w.numel() else 0.0
+        if zero_by_softmax_symmetry(k):
+            if err > KEY_BIAS_ABS or scale > KEY_BIAS_ABS:
+                bad.append((k, err, scale))
+            continue
+        n32 = float(noise32.get(k, 0.0)) if noise32 is not None else 0.0
+        if err > max(rel * scale, 2 * n32) + 1e-7:
+            bad.append((k, err, scale, n32))
+        r = err / max(scale, 1e-7 / rel)
+        if r > worst[0]:
+            worst = (r, k, err)
+    print(f"[trained-backward] {tag}: worst {worst[1]} {worst[0]:.2e} of its max ({worst[2]:.1e}); {len(got)} tensors, {len(bad)} over")
+    return bad
+
+
+# the end-to-end training-step cases at trained-like weights (tests/test_gpu_trained_backward.py, tests/test_trained_grad_profile_cpu.py)
+TRAINED_STEP_CASES = ("mixed_k6_t20", "shipped_k10_t60")
+TRAINED_STEP_MODES = ("eval", "dropout", "nll")
+TRAINED_STEP_SEED = 31
+
+
+def trained_step_case(name, mode, strength):
+    """(model in eval mode on the host, cfg, batch, oracle_full_grads keyword arguments) of one end-to-end case: TRAINED_CASES[name]
+    at trained_like_parameters(strength), loss weights [1, 0.5]; `mode` "eval", "dropout" (train mode with the YAML's dropout 0.1,
+    masks keyed by the noise seed TRAINED_STEP_SEED) or "nll" (losses_module: [LaplaceNLLLoss, DiffBCE], eps 1e-6)"""
+    import restate
+    from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet
+    K, T, max_t, make = TRAINED_CASES[name]
+    cfg = our_cfg(K, T, max_t)
+    kw = {}
+    if mode == "nll":
+        cfg["losses_module"] = ["LaplaceNLLLoss", "DiffBCE"]
+        cfg["loss_args"] = [{"eps": 1e-6, "reduction": "mean"}, {"reduction": "mean"}]
+        kw["nll_eps"] = 1e-6
+    elif mode == "dropout":
+        assert cfg["encoder"]["kwargs"]["dropout"] == cfg["aggregator"]["kwargs"]["dropout"] == 0.1
+        kw["drop"] = restate.PhiloxDropout(TRAINED_STEP_SEED, 0.1)
+    model = PredictionModelSDENet(**cfg, init_seed=2).eval()
+    model.loss_weights = [1.0, 0.5]
+    trained_like_parameters(model, TRAINED_SEED, strength)
+    return model, cfg, make(), kw
