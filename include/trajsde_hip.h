@@ -75,7 +75,9 @@ typedef enum {
   TRAJSDE_STAGE_ENCODER_GRID_BWD = 9, /* trajsde_encoder_grid_backward; num_layers = temporal layers */
   TRAJSDE_STAGE_DECODER_NLL_BWD = 10, /* trajsde_decoder_nll_backward: the DECODER_BWD table followed by the scale head (ABI 8) */
   TRAJSDE_STAGE_DECODER_MILSTEIN = 11, /* trajsde_decoder_forward_milstein: the DECODER table; its blob + GFunc's transposes (ABI 10) */
-  TRAJSDE_STAGE_DECODER_MLP_NLL_BWD = 12 /* trajsde_mlp_decoder_nll_backward: the DECODER_MLP_BWD table followed by the scale head (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MLP_NLL_BWD = 12, /* trajsde_mlp_decoder_nll_backward: the DECODER_MLP_BWD table followed by the scale head (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MILSTEIN_BWD = 13, /* trajsde_decoder_l2_backward_milstein: the DECODER_BWD table; its blob + GFunc's tangent images (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD = 14 /* trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; its blob + the same (ABI 10) */
 } trajsde_stage;
 
 int trajsde_param_count(int stage, int num_layers /*aggregator*/, int num_modes);
@@ -395,6 +397,24 @@ int trajsde_decoder_nll_backward(int32_t N, int num_modes, int future_steps, con
                                  const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
                                  const uint8_t* reg_mask, float eps, float min_scale, void* ws, int64_t ws_bytes, float* loss,
                                  int32_t* best_mode, float* const* grads, int n_grads, float* d_local, float* d_global, void* stream);
+
+/* Added at ABI 10: the two entry points above for a decoder solved with `method: milstein` (trajsde_decoder_forward_milstein), same
+ * arguments.  `blob_fwd` is the TRAJSDE_STAGE_DECODER_MILSTEIN image, `blob_bwd` the TRAJSDE_STAGE_DECODER_MILSTEIN_BWD (L2) or
+ * _MILSTEIN_NLL_BWD (Laplace NLL) image, whose parameter tables -- and so the order of `grads` -- are those of DECODER_BWD and
+ * DECODER_NLL_BWD.  The winning paths are replayed with the Milstein step and the reverse sweep differentiates its gdg term too
+ * (torchsde's vjp with create_graph: second derivatives of GFunc).  The workspace query covers both losses. */
+int64_t trajsde_decoder_milstein_backward_ws_bytes(int32_t N, int num_modes, int future_steps, int n_euler);
+int trajsde_decoder_l2_backward_milstein(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
+                                         const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
+                                         const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
+                                         const uint8_t* reg_mask, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode,
+                                         float* const* grads, int n_grads, float* d_local, float* d_global, void* stream);
+int trajsde_decoder_nll_backward_milstein(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
+                                          const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
+                                          const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
+                                          const uint8_t* reg_mask, float eps, float min_scale, void* ws, int64_t ws_bytes, float* loss,
+                                          int32_t* best_mode, float* const* grads, int n_grads, float* d_local, float* d_global,
+                                          void* stream);
 
 /* ---- backward of the aggregator stage (AGG:38-58, 92-135): dL/d global_embed -> dL/d local_embed (overwritten;
  *      the caller adds the decoder's own d local_embed) and one gradient per aggregator parameter, grads[i] shaped

@@ -15,6 +15,8 @@ STAGE_ENCODER_GRID, STAGE_DECODER_MLP, STAGE_DECODER_MLP_BWD, STAGE_ENCODER_GRID
 STAGE_DECODER_NLL_BWD = 10
 STAGE_DECODER_MILSTEIN = 11   # trajsde_decoder_forward_milstein: the decoder blob + GFunc's transposed matrices (added at ABI 10)
 STAGE_DECODER_MLP_NLL_BWD = 12   # trajsde_mlp_decoder_nll_backward: the MLP decoder's L2 table + the scale head (added at ABI 10)
+STAGE_DECODER_MILSTEIN_BWD = 13      # trajsde_decoder_l2_backward_milstein: the DECODER_BWD table; + GFunc's tangent images (ABI 10)
+STAGE_DECODER_MILSTEIN_NLL_BWD = 14  # trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; + the same (ABI 10)
 
 
 ABI_VERSION = 10         # trajsde_graph grew aa_src / la_lane (2); trajsde_dropout arguments (3); training tapes (4);
@@ -107,6 +109,11 @@ SIGNATURES = {
     "trajsde_decoder_nll_backward_ws_bytes": (I64, [I32, C.c_int, C.c_int, C.c_int]),
     "trajsde_decoder_nll_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, C.POINTER(Noise), P, P, P, F32, F32, P, I64,
                                                P, P, C.POINTER(P), C.c_int, P, P, P]),
+    "trajsde_decoder_milstein_backward_ws_bytes": (I64, [I32, C.c_int, C.c_int, C.c_int]),
+    "trajsde_decoder_l2_backward_milstein": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, C.POINTER(Noise), P, P, P, P, I64,
+                                                       P, P, C.POINTER(P), C.c_int, P, P, P]),
+    "trajsde_decoder_nll_backward_milstein": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, C.POINTER(Noise), P, P, P, F32, F32,
+                                                        P, I64, P, P, C.POINTER(P), C.c_int, P, P, P]),
     "trajsde_aggregator_backward_ws_bytes": (I64, [C.POINTER(Batch), C.POINTER(Graph), C.c_int, C.c_int]),
     "trajsde_aggregator_backward": (C.c_int, [C.POINTER(Batch), C.POINTER(Graph), P, P, C.c_int, C.c_int, P, P, P, I64,
                                               C.POINTER(P), C.c_int, P, P]),

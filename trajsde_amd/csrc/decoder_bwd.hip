@@ -15,6 +15,8 @@
 //   k_dec_init_bwd             aggr_embed backward: d local_embed, d global_embed, saves (input, da)
 //   k_wgrad / k_reduce_partials   dW = sum_rows delta^T a  as MFMA outer products over saved rows (deterministic
 //                              two-stage reduction), bias = column sums, time-feature columns = step-weighted sums
+// `method: milstein` (trajsde_decoder_*_backward_milstein) runs the same host code with the replay and the sweep of
+// decoder_mil_bwd.hip (the Milstein step and its gdg term) and two more weight-gradient products.
 //
 // Matrix products run on transposed images (layouts.hpp SweepL / HeadBwdL / InitBwdL): dX^T = W^T dY^T has the same
 // "row on lane" operand/result layout as the forward.  tile.hpp linear_adj: row-scaled split precision in the fp16x3
@@ -1454,10 +1456,12 @@ struct BwdWs {
   int32_t *best, *cnt;
   float *minsum, *scal, *states, *H1, *H2, *G1, *G2, *GS, *DH1, *DH2, *DF, *DG1, *DG2, *S_in, *DU, *DS, *gsel, *DA, *DY0, *part, *cs,
       *vpart, *DU2, *varena;
+  MilRows mil;                                             // Milstein only: the sweep's extra rows (k_sde_bwd_mil)
+  float *MW2, *MW0;                                        // ... and their two 64 x 64 weight-gradient blocks
   int64_t bytes, parts, varena_floats;
 };
 
-BwdWs carve_bwd(void* ws, int64_t ws_bytes, int N, int T, int n_euler, bool& ok, bool nll = false) {
+BwdWs carve_bwd(void* ws, int64_t ws_bytes, int N, int T, int n_euler, bool& ok, bool nll = false, bool mil = false) {
   Carver cv(ws, ws_bytes);
   BwdWs w;
   const int64_t slab = int64_t(N) * 64;
@@ -1490,6 +1494,16 @@ BwdWs carve_bwd(void* ws, int64_t ws_bytes, int N, int T, int n_euler, bool& ok,
   w.varena_floats = VPART_ARENA_SLABS * int64_t(256) * (BWD_THREADS / 64) * 512;
   w.varena = cv.take<float>(w.varena_floats);
   w.DU2 = nll ? cv.take<float>(slab * T) : nullptr;        // the scale head's delta rows (Laplace NLL)
+  w.mil = MilRows{nullptr, nullptr, nullptr, nullptr};
+  w.MW2 = w.MW0 = nullptr;
+  if (mil) {
+    w.mil.g2b = cv.take<float>(slab * n_euler);
+    w.mil.h1t = cv.take<float>(slab * n_euler);
+    w.mil.g1b = cv.take<float>(slab * n_euler);
+    w.mil.u = cv.take<float>(slab * n_euler);
+    w.MW2 = cv.take<float>(4096);
+    w.MW0 = cv.take<float>(4096);
+  }
   w.bytes = cv.off + 256;
   ok = cv.ok;
   return w;
@@ -1517,11 +1531,17 @@ int64_t trajsde_decoder_nll_backward_ws_bytes(int32_t N, int num_modes, int futu
   return carve_bwd(nullptr, 0, N, future_steps, n_euler, ok, true).bytes;
 }
 
+int64_t trajsde_decoder_milstein_backward_ws_bytes(int32_t N, int num_modes, int future_steps, int n_euler) {
+  (void)num_modes;
+  bool ok;
+  return carve_bwd(nullptr, 0, N, future_steps, n_euler, ok, true, true).bytes;      // (either loss)
+}
+
 static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N, int num_modes, int future_steps, const float* blob_fwd,
                                  const float* blob_bwd, const float* local_embed, const float* global_embed, const float* step_table,
                                  int n_euler, const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
                                  const uint8_t* reg_mask, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads,
-                                 int n_grads, float* d_local, float* d_global, void* stream_);
+                                 int n_grads, float* d_local, float* d_global, void* stream_, bool milstein = false);
 
 int trajsde_decoder_l2_backward(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
                                 const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
@@ -1543,11 +1563,35 @@ int trajsde_decoder_nll_backward(int32_t N, int num_modes, int future_steps, con
                                stream_);
 }
 
+int trajsde_decoder_l2_backward_milstein(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
+                                         const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
+                                         const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
+                                         const uint8_t* reg_mask, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode,
+                                         float* const* grads, int n_grads, float* d_local, float* d_global, void* stream_) {
+  return decoder_backward_impl(false, 0.f, 0.f, N, num_modes, future_steps, blob_fwd, blob_bwd, local_embed, global_embed, step_table, n_euler,
+                               out_table, noise, loc, y, reg_mask, ws, ws_bytes, loss, best_mode, grads, n_grads, d_local, d_global, stream_,
+                               true);
+}
+
+int trajsde_decoder_nll_backward_milstein(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
+                                          const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
+                                          const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
+                                          const uint8_t* reg_mask, float eps, float min_scale, void* ws, int64_t ws_bytes, float* loss,
+                                          int32_t* best_mode, float* const* grads, int n_grads, float* d_local, float* d_global,
+                                          void* stream_) {
+  TS_REQUIRE(eps > 0.f, "decoder_nll_backward: eps must be positive");
+  return decoder_backward_impl(true, eps, min_scale, N, num_modes, future_steps, blob_fwd, blob_bwd, local_embed, global_embed, step_table,
+                               n_euler, out_table, noise, loc, y, reg_mask, ws, ws_bytes, loss, best_mode, grads, n_grads, d_local, d_global,
+                               stream_, true);
+}
+
+// milstein: blob_fwd is a TRAJSDE_STAGE_DECODER_MILSTEIN image, blob_bwd a _MILSTEIN_BWD / _MILSTEIN_NLL_BWD one; the replay and the
+// sweep take their one-wave Milstein kernels (the cooperative forms are Euler-only), two more weight-gradient products join the batch
 static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N, int num_modes, int future_steps, const float* blob_fwd,
                                  const float* blob_bwd, const float* local_embed, const float* global_embed, const float* step_table,
                                  int n_euler, const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
                                  const uint8_t* reg_mask, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads,
-                                 int n_grads, float* d_local, float* d_global, void* stream_) {
+                                 int n_grads, float* d_local, float* d_global, void* stream_, bool milstein) {
   TS_REQUIRE(blob_fwd && blob_bwd && local_embed && global_embed && step_table && out_table && loc && y && reg_mask && ws && loss &&
                  grads && d_local && d_global,
              "decoder backward: null pointer");
@@ -1555,13 +1599,14 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
   const int want_grads = nll ? int(N_GRADS_NLL) : int(N_GRADS);
   TS_REQUIRE(n_grads == want_grads, "decoder backward: gradient count does not match trajsde_param_count of the backward stage");
   for (int i = 0; i < want_grads; ++i) TS_REQUIRE(grads[i] != nullptr, "decoder backward: null gradient buffer");
-  if (ws_bytes < (nll ? trajsde_decoder_nll_backward_ws_bytes(N, num_modes, future_steps, n_euler)
-                      : trajsde_decoder_backward_ws_bytes(N, num_modes, future_steps, n_euler)))
+  if (ws_bytes < (milstein ? trajsde_decoder_milstein_backward_ws_bytes(N, num_modes, future_steps, n_euler)
+                  : nll    ? trajsde_decoder_nll_backward_ws_bytes(N, num_modes, future_steps, n_euler)
+                           : trajsde_decoder_backward_ws_bytes(N, num_modes, future_steps, n_euler)))
     return fail(TRAJSDE_ERR_WORKSPACE, "decoder backward: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   bool ok;
   const int K = num_modes, T = future_steps;
-  BwdWs w = carve_bwd(ws, ws_bytes, N, T, n_euler, ok, nll);
+  BwdWs w = carve_bwd(ws, ws_bytes, N, T, n_euler, ok, nll || milstein, milstein);
   DeferredSums sums(st, w.part, w.cs, w.parts, step_table, w.varena, w.varena_floats);      // every reduction of this call: at the end
   NoiseArg na{0, nullptr, nullptr};
   if (noise) { na.seed = noise->seed; na.z = noise->z; na.row_ids = noise->row_ids; na.seed_dev = noise->seed_dev; }
@@ -1593,6 +1638,12 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
   // the cooperative form (recur.hip k_sde_replay_coop: four waves a tile, the fused forward kernel's own image); TRAJSDE_REPLAY_COOP=0:
   // the one-wave kernel of this file
   static const bool replay_coop = []() { const char* e = getenv("TRAJSDE_REPLAY_COOP"); return !(e && e[0] == '0'); }();
+#endif
+  if (milstein)                                            // (Milstein: the one-wave kernel, MilL staged behind the plain images)
+    TS_LAUNCH(k_sde_replay_mil, bwd_grid(ntiles), BWD_THREADS, (DecSdeL::LOC + MilL::SIZE) * 4, st, blob_fwd + DecBlob::SDE,
+              blob_fwd + DecMilBlob::MIL, w.best, N, K, n_euler, step_table, na, w.states, w.H1, w.H2, w.G1, w.G2, w.GS);
+  else
+#if TSDE_SPLIT_H3
   if (replay_coop)
     TS_LAUNCH_TAG("k_sde_replay", false, k_sde_replay_coop, ntiles < 8192 ? ntiles : 8192, 256, SDE_REPLAY_COOP_LDS_BYTES, st,
                   blob_fwd + DecBlob::SDE6, w.best, N, K, n_euler, step_table, na, w.states, w.H1, w.H2, w.G1, w.G2, w.GS);
@@ -1637,7 +1688,7 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
 #if TSDE_SPLIT_H3
   // the cooperative form (recur.hip k_sde_bwd_coop: four waves a tile); TRAJSDE_SWEEP_COOP=0: the one-wave kernel of this file
   static const bool sweep_coop_env = []() { const char* e = getenv("TRAJSDE_SWEEP_COOP"); return !(e && e[0] == '0'); }();
-  bool sweep_coop = sweep_coop_env;
+  bool sweep_coop = sweep_coop_env && !milstein;
 #else
   bool sweep_coop = false;
 #endif
@@ -1655,6 +1706,10 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
     const SdeBwdCoopArgs ca{blob_bwd + DecBwdBlob::SWEEP, w.best, N, K, T, n_euler, step_table, out_table, na, w.H1, w.H2, w.G1, w.G2, w.GS,
                             w.DS, w.DH1, w.DH2, w.DF, w.DG1, w.DG2, w.DY0, vp};
     TS_LAUNCH_TAG("k_sde_bwd", false, k_sde_bwd_coop, sweep_rows, 256, int(coop_lds), st, ca);
+  } else if (milstein) {
+    const float* tan_img = blob_bwd + (nll ? int(DecMilNllBwdBlob::TAN) : int(DecMilBwdBlob::TAN));
+    TS_LAUNCH(k_sde_bwd_mil, sweep_grid, BWD_THREADS, (SweepL::SIZE + TanL::SIZE) * 4, st, blob_bwd + DecBwdBlob::SWEEP, tan_img, w.best, N, K,
+              T, n_euler, step_table, out_table, na, w.H1, w.H2, w.G1, w.G2, w.GS, w.DS, w.DH1, w.DH2, w.DF, w.DG1, w.DG2, w.DY0, vp, w.mil);
   } else {
     TS_LAUNCH(k_sde_bwd, sweep_grid, BWD_THREADS, SweepL::SIZE * 4, st, blob_bwd + DecBwdBlob::SWEEP, w.best, N, K, T, n_euler, step_table,
               out_table, na, w.H1, w.H2, w.G1, w.G2, w.GS, w.DS, w.DH1, w.DH2, w.DF, w.DG1, w.DG2, w.DY0, vp);
@@ -1690,6 +1745,10 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
     if ((rc = sde.add(w.DF, 64, w.H2, 64, grads[F4W], 64, 0, grads[F4B], 0))) return rc;
     if ((rc = sde.add(w.DG1, 64, w.states, 64, grads[G0W], 66, 0, grads[G0B], 1))) return rc;
     if ((rc = sde.add(w.DG2, 64, w.G1, 64, grads[G2W], 64, 0, grads[G2B], 0))) return rc;
+    if (milstein) {                                         // the gdg term's products, into blocks of their own (k_add_mil_wgrad)
+      if ((rc = sde.add(w.mil.g2b, 64, w.mil.h1t, 64, w.MW2, 64, 0, nullptr, 0))) return rc;
+      if ((rc = sde.add(w.mil.g1b, 64, w.mil.u, 64, w.MW0, 64, 0, nullptr, 0))) return rc;
+    }
     if ((rc = sde.flush())) return rc;
   }
   if ((rc = wgrad(w.DU, w.S_in, RT, RT, grads[D0W], 64, 0, grads[D0B], 0))) return rc;
@@ -1700,7 +1759,9 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
     if ((rc = init.add(w.DA, 64, local_embed, 64, grads[A0W], 128, 64, nullptr, 0))) return rc;
     if ((rc = init.flush())) return rc;
   }
-  return sums.finish();
+  if ((rc = sums.finish())) return rc;
+  if (milstein) TS_LAUNCH(k_add_mil_wgrad, 32, 256, 0, st, grads[G2W], grads[G0W], w.MW2, w.MW0);
+  return TRAJSDE_OK;
 }
 
 }  // extern "C"

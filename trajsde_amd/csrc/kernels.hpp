@@ -236,6 +236,18 @@ struct SdeBwdCoopArgs {
   float *DH1, *DH2, *DF, *DG1, *DG2, *DY0, *vpart;     // vpart: one row of SweepV::SIZE floats per WORKGROUP
 };
 __global__ void k_sde_bwd_coop(SdeBwdCoopArgs a);
+// the decoder backward under `method: milstein` (decoder_mil_bwd.hip): the replay with the Milstein step (MilL staged behind the plain
+// drift + diffusion images), the sweep through it (TanL staged behind SweepL; SweepV rows as k_sde_bwd), the join of its two extra
+// weight-gradient blocks.  MilRows: per (step, row) the rows of those two products, [n_euler][N][64] each: g2b = dPsi/da2' and h1t = h1'
+// (g_func.net.2.weight), g1b = dPsi/da1' and u = dL/dy_{k+1} (the y-columns of g_func.net.0.weight)
+struct MilRows { float *g2b, *h1t, *g1b, *u; };
+__global__ void k_sde_replay_mil(const float* img, const float* mil_img, const int32_t* best, int N, int K, int n_euler, const float* step_tab,
+                                 NoiseArg na, float* states, float* H1, float* H2, float* G1, float* G2, float* GS);
+__global__ void k_sde_bwd_mil(const float* img, const float* tan_img, const int32_t* best, int N, int K, int T, int n_euler, const float* step_tab,
+                              const float* out_tab, NoiseArg na, const float* H1, const float* H2, const float* G1, const float* G2,
+                              const float* GS, const float* DS, float* DH1, float* DH2, float* DF, float* DG1, float* DG2, float* DY0,
+                              float* vpart, MilRows mr);
+__global__ void k_add_mil_wgrad(float* w2, float* w0, const float* m2, const float* m0);
 // vanilla HiVT variant (grid.hip)
 __global__ void k_tr_prep(const float* aa_out, const uint8_t* pad, const float* tok, int N, int TT, float* X);
 template <int HEADS, bool DROP>

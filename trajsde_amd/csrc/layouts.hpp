@@ -425,6 +425,22 @@ struct DecBwdBlob {
 struct DecNllBwdBlob {   // Laplace NLL: the L2 blob followed by the scale head's images (forward + W0 transposed)
   enum : int { HEAD_SC = DecBwdBlob::SIZE, SIZE = HEAD_SC + HeadBwdL::SIZE };
 };
+// Milstein reverse sweep (decoder_bwd.hip sde_bwd_body<true>): the tangent pass of GFunc along the adjoint u -- W0y u, W2 h1' -- runs
+// through linear_adj on GFunc's y-columns of net.0 and net.2 UNTRANSPOSED and unscaled (the orientation linear_adj reads as W, where
+// the SweepL `*T` fields give W^T).  The TRAJSDE_STAGE_DECODER_MILSTEIN_BWD / _NLL_BWD blobs are the Euler backward blobs with this
+// image appended; in LDS it sits right behind the sweep image.
+struct TanL {
+  enum : int { S_END = 0, TS_FIELD(G_W0, MAT64, S), TS_FIELD(G_W2, MAT64, G_W0), SIZE = G_W2_END };
+};
+struct DecMilBwdBlob {
+  enum : int { TAN = DecBwdBlob::SIZE, SIZE = TAN + TanL::SIZE };
+};
+struct DecMilNllBwdBlob {
+  enum : int { TAN = DecNllBwdBlob::SIZE, SIZE = TAN + TanL::SIZE };
+};
+static_assert(DecMilBwdBlob::TAN % 4 == 0 && DecMilNllBwdBlob::TAN % 4 == 0 && (SweepL::SIZE + TanL::SIZE) * 4 <= 160 * 1024,
+              "Milstein sweep image: aligned, fits LDS beside the sweep image");
+static_assert((DecSdeL::LOC + MilL::SIZE) * 4 <= 160 * 1024, "Milstein replay: drift + diffusion images and MilL fit LDS");
 // ---- backward images of the node-level blocks shared by the three attention families (node_bwd.hip)
 struct FfnBwdAL {     // recompute h = relu(W1 xn2 + b1), dh = (W2^T dout) * (h > 0)
   enum : int { S_END = 0, TS_FIELD(W1, 4 * MAT64, S), TS_FIELD(B1, 256, W1), TS_FIELD(W2T, 4 * MAT64, B1), SIZE = W2T_END };

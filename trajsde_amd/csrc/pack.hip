@@ -925,6 +925,21 @@ static void recipe_decoder_nll_bwd(Packer& P) {
   P.matT("scale.0.weight", h + HeadBwdL::W0T, 64);
 }
 
+// Milstein backward (either loss): the Euler backward's table and images, then GFunc's net.0 (y-columns) and net.2 untransposed and
+// unscaled for the sweep's tangent pass (layouts.hpp TanL); the parameter table is the Euler one (both tensors are already in it)
+static void recipe_tangent(Packer& P, int t) {
+  P.mat("lsde_func.g_func.net.0.weight", t + TanL::G_W0, 64, 64, 66, 0);
+  P.mat("lsde_func.g_func.net.2.weight", t + TanL::G_W2, 64, 64, 64, 0);
+}
+static void recipe_decoder_milstein_bwd(Packer& P) {
+  recipe_decoder_bwd(P);
+  recipe_tangent(P, DecMilBwdBlob::TAN);
+}
+static void recipe_decoder_milstein_nll_bwd(Packer& P) {
+  recipe_decoder_nll_bwd(P);
+  recipe_tangent(P, DecMilNllBwdBlob::TAN);
+}
+
 // node-level backward images of one attention block (layouts.hpp NodeBlockBwdL); `p` = the block's parameter prefix
 static void recipe_node_block_bwd(Packer& P, const std::string& p, int base) {
   const int a = base + NodeBlockBwdL::FFN_A, b = base + NodeBlockBwdL::FFN_B, u = base + NodeBlockBwdL::UPD;
@@ -1085,6 +1100,8 @@ static bool run_recipe(Packer& P, int stage, int nl, int K) {
     case TRAJSDE_STAGE_DECODER_MILSTEIN: recipe_decoder_milstein(P); return true;
     case TRAJSDE_STAGE_DECODER_BWD: recipe_decoder_bwd(P); return true;
     case TRAJSDE_STAGE_DECODER_NLL_BWD: recipe_decoder_nll_bwd(P); return true;
+    case TRAJSDE_STAGE_DECODER_MILSTEIN_BWD: recipe_decoder_milstein_bwd(P); return true;
+    case TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD: recipe_decoder_milstein_nll_bwd(P); return true;
     case TRAJSDE_STAGE_AGGREGATOR_BWD: recipe_aggregator_bwd(P, nl, K); return true;
     case TRAJSDE_STAGE_ENCODER_BWD: recipe_encoder_bwd(P); return true;
     case TRAJSDE_STAGE_ENCODER_GRID: recipe_encoder_grid(P, nl); return true;
@@ -1220,6 +1237,8 @@ int64_t trajsde_blob_floats(int stage, int num_layers, int num_modes) {
     case TRAJSDE_STAGE_DECODER_MILSTEIN: return DecMilBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_BWD: return DecBwdBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_NLL_BWD: return DecNllBwdBlob::SIZE;
+    case TRAJSDE_STAGE_DECODER_MILSTEIN_BWD: return DecMilBwdBlob::SIZE;
+    case TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD: return DecMilNllBwdBlob::SIZE;
     case TRAJSDE_STAGE_AGGREGATOR_BWD: return AggBwdBlob::size(num_layers, num_modes);
     case TRAJSDE_STAGE_ENCODER_BWD: return EncBwdBlob::SIZE;
     case TRAJSDE_STAGE_ENCODER_GRID: return EncGridBlob::size(num_layers);

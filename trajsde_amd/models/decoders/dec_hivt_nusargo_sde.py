@@ -3,7 +3,8 @@ embeddings into y0 [K*N,64], Euler-Maruyama over the future grid with learned dr
 scalar-broadcast diffusion (Euler-Maruyama or Milstein), heads -> loc/scale/pi.
 
 `method: euler` (the shipped one) or `method: milstein` (torchsde's MilsteinIto: the same fixed-step schedule and noise, plus the
-column-sum gdg term of the scalar-broadcast diffusion; inference only -- training refuses it).
+column-sum gdg term of the scalar-broadcast diffusion; trained through the Milstein backward, whose reverse sweep differentiates
+that term as torchsde's create_graph vjp does).
 Constructor kwargs as in configs/nusargo/hivt_nuSArgo_sdesepenc_sdedec.yml:64-76; call signature
 `decoder(data=..., local_embed=..., global_embed=...) -> {'loc','pi','reg_mask'}`; `uncertain: False` (DEC:56, DEC:100-101):
 no `scale.*` parameters and `loc` [K, N, T, 2] -- the kernels run with a zero stand-in head and the scale channels are dropped.

@@ -231,12 +231,18 @@ class PredictionModelSDENet(LightningHooks):
     def _step_pack_set(self) -> "runtime.PackSet":
         """forward and backward images of the three stages, as one packing call per optimizer step"""
         from trajsde_amd import _lib
-        dec_stage = _lib.STAGE_DECODER_NLL_BWD if self._regression_loss()[0] == "LaplaceNLLLoss" else _lib.STAGE_DECODER_BWD
+        nll = self._regression_loss()[0] == "LaplaceNLLLoss"
+        if getattr(self.decoder, "method", "euler") == "milstein":   # the Milstein images (the stage ids tell the two sets apart)
+            dec_fwd = _lib.STAGE_DECODER_MILSTEIN
+            dec_stage = _lib.STAGE_DECODER_MILSTEIN_NLL_BWD if nll else _lib.STAGE_DECODER_MILSTEIN_BWD
+        else:
+            dec_fwd = _lib.STAGE_DECODER
+            dec_stage = _lib.STAGE_DECODER_NLL_BWD if nll else _lib.STAGE_DECODER_BWD
         ps = self.__dict__.get("_pack_set_obj")
         if ps is None or ps.entries[-1][1] != dec_stage:
             enc_rt, agg_rt, dec_rt = self.encoder._rt, self.aggregator._rt, self.decoder._rt
             ps = runtime.PackSet([(enc_rt, _lib.STAGE_ENCODER), (enc_rt, _lib.STAGE_ENCODER_BWD), (agg_rt, _lib.STAGE_AGGREGATOR),
-                                  (agg_rt, _lib.STAGE_AGGREGATOR_BWD), (dec_rt, _lib.STAGE_DECODER), (dec_rt, dec_stage)])
+                                  (agg_rt, _lib.STAGE_AGGREGATOR_BWD), (dec_rt, dec_fwd), (dec_rt, dec_stage)])
             self.__dict__["_pack_set_obj"] = ps
         return ps
 
@@ -308,7 +314,8 @@ class PredictionModelSDENet(LightningHooks):
         reference's sites (attention weights, out_proj output, the two FFN activations of every attention block) with masks
         cut from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()` switches it off, as in the reference.  The kernels implement the
         shipped loss set (losses/L2.py + losses/diff_BCE.py, CFG:78-83) and losses/laplace_nll_loss.py in place of L2; any other loss
-        is refused rather than silently differentiated elsewhere.  So is a decoder with `method: milstein` (inference only)."""
+        is refused rather than silently differentiated elsewhere.  A decoder with `method: milstein` trains too (its reverse sweep
+        differentiates the gdg term: trajsde_decoder_*_backward_milstein), on the GPU only."""
         runtime.refuse_milstein_training(self.decoder)
         if not self.rotate:
             raise NotImplementedError("rotate=False is not built (shipped config: rotate: true, CFG:18)")

@@ -467,11 +467,16 @@ class PackSet:
             rt._blobs[sid] = (blob, stamp, ev, cur.cuda_stream)
 
 
-def refuse_milstein_training(decoder) -> None:
-    """the Milstein decoder is built for inference: differentiating its gdg term needs Hessian-vector products of GFunc"""
-    if getattr(decoder, "method", "euler") == "milstein":
-        raise NotImplementedError("training a decoder with `method: milstein` is not built: the gradient of its gdg term needs "
-                                  "Hessian-vector products of GFunc (inference is supported)")
+def refuse_milstein_training(decoder, local_embed=None, need_embed: bool = False) -> None:
+    """a decoder with `method: milstein` trains through the HIP kernels alone (trajsde_decoder_*_backward_milstein): refused where they
+    cannot run -- parameters, or the stage input `local_embed` (`need_embed`: it must be given), not on the GPU"""
+    if getattr(decoder, "method", "euler") != "milstein":
+        return
+    first = decoder._rt._first_param()
+    missing = need_embed and (local_embed is None or not getattr(local_embed, "is_cuda", False))
+    if not first.is_cuda or missing:
+        raise NotImplementedError("training a decoder with `method: milstein` runs on the GPU only (the reverse sweep through its gdg term "
+                                  "is a HIP kernel): parameters and inputs must be on the GPU")
 
 
 class StageRuntime:
@@ -653,8 +658,9 @@ class StageRuntime:
 
     def _decoder_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
                           noise: NoiseSpec, nll_eps: Optional[float]) -> Dict[str, object]:
-        """shared body of decoder_l2_backward / decoder_nll_backward (`nll_eps` None: L2)"""
-        refuse_milstein_training(self.module)
+        """shared body of decoder_l2_backward / decoder_nll_backward (`nll_eps` None: L2); `method: milstein` takes the Milstein
+        entry points on the Milstein images (the forward's, and the backward's with GFunc's tangent images appended)"""
+        refuse_milstein_training(self.module, local_embed, need_embed=True)
         m = self.module
         if noise is None:
             raise _lib.TrajsdeError("decoder_l2_backward needs the NoiseSpec of the forward pass (seed or z_dec)")
@@ -676,27 +682,37 @@ class StageRuntime:
         stage = _lib.STAGE_DECODER_BWD if nll_eps is None else _lib.STAGE_DECODER_NLL_BWD
         names = self.param_names(stage)
         grads = self._grad_buffers(stage)
+        milstein = m.method == "milstein"
+        if milstein:                       # (the same parameter tables: the gradient buffers and their order are the Euler ones)
+            fwd_stage = _lib.STAGE_DECODER_MILSTEIN
+            blob_stage = _lib.STAGE_DECODER_MILSTEIN_BWD if nll_eps is None else _lib.STAGE_DECODER_MILSTEIN_NLL_BWD
+        else:
+            fwd_stage, blob_stage = self.stage_id, stage
         arr, _keep = grads.pointer_array()
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         best = torch.empty(N, device=dev, dtype=torch.int32)
         d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
         d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
         cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
-        head = (N, K, T, self.blob().data_ptr(), self.blob(stage).data_ptr(),
+        head = (N, K, T, self.blob(fwd_stage).data_ptr(), self.blob(blob_stage).data_ptr(),
                 local_embed.contiguous().data_ptr(), global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler,
                 out_tab.data_ptr(), C.byref(cn), _loc4(out).data_ptr(), y.data_ptr(), mask.data_ptr())
+        sfx = "_milstein" if milstein else ""
+        if milstein:                                     # (one workspace query covers both losses)
+            ws_query = L.trajsde_decoder_milstein_backward_ws_bytes
+        else:
+            ws_query = L.trajsde_decoder_backward_ws_bytes if nll_eps is None else L.trajsde_decoder_nll_backward_ws_bytes
+        ws_bytes = ws_query(N, K, T, sched.n_euler)
         with torch.cuda.device(dev):
+            ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
             if nll_eps is None:
-                ws_bytes = L.trajsde_decoder_backward_ws_bytes(N, K, T, sched.n_euler)
-                ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-                _lib.check(L.trajsde_decoder_l2_backward(*head, ws.data_ptr(), ws_bytes, loss.data_ptr(), best.data_ptr(), arr, len(names),
-                                                         d_local.data_ptr(), d_global.data_ptr(), _stream()), "trajsde_decoder_l2_backward")
+                name = "trajsde_decoder_l2_backward" + sfx
+                _lib.check(getattr(L, name)(*head, ws.data_ptr(), ws_bytes, loss.data_ptr(), best.data_ptr(), arr, len(names),
+                                            d_local.data_ptr(), d_global.data_ptr(), _stream()), name)
             else:
-                ws_bytes = L.trajsde_decoder_nll_backward_ws_bytes(N, K, T, sched.n_euler)
-                ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-                _lib.check(L.trajsde_decoder_nll_backward(*head, float(nll_eps), float(m.min_scale), ws.data_ptr(), ws_bytes, loss.data_ptr(),
-                                                          best.data_ptr(), arr, len(names), d_local.data_ptr(), d_global.data_ptr(),
-                                                          _stream()), "trajsde_decoder_nll_backward")
+                name = "trajsde_decoder_nll_backward" + sfx
+                _lib.check(getattr(L, name)(*head, float(nll_eps), float(m.min_scale), ws.data_ptr(), ws_bytes, loss.data_ptr(),
+                                            best.data_ptr(), arr, len(names), d_local.data_ptr(), d_global.data_ptr(), _stream()), name)
         return {"loss": loss[0], "best_mode": best, "grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
 
     # ---------------------------------------------------------------- encoder
