@@ -1,7 +1,8 @@
 """CPU restatement of TrajSDE's forward hot path -- TEST INFRASTRUCTURE ONLY.
 
-Plain torch on the host, in the dtype of the weights and the batch (fp32 for the fixtures, float64 as a reference for the
-kernels' own error: tests/helpers.py oracle_forward64).  This file is the *checker*: only tests/, __graft_entry__.smoke() and
+Plain torch in the dtype and on the device of the weights and the batch (fp32 on the host for the fixtures, float64 as a
+reference for the kernels' own error: tests/helpers.py oracle_forward64, on the host or, for whole full-size batches, on the GPU:
+tests/test_gpu_full_size_oracle.py).  The Philox twins compute on the host and hand their result to the inputs' device.  This file is the *checker*: only tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg may import it.  The product path (trajsde_amd/) never does.
 
 Parity pin: validated <= 1e-5 against golden vectors produced by running the reference's own modules
@@ -72,12 +73,14 @@ class PhiloxDropout:
 
     def attn(self, block, src, dst, heads, like):
         from trajsde_amd import philox
-        rank = philox.segment_ranks(src.numpy(), dst.numpy())
-        return torch.from_numpy(philox.dropout_attn_mask(self.seed, block, dst.numpy(), rank, heads, self.p)).to(like.dtype)
+        src, dst = src.cpu().numpy(), dst.cpu().numpy()
+        rank = philox.segment_ranks(src, dst)
+        return torch.from_numpy(philox.dropout_attn_mask(self.seed, block, dst, rank, heads, self.p)).to(like.device, like.dtype)
 
     def feat(self, block, kind, like):
         from trajsde_amd import philox
-        return torch.from_numpy(philox.dropout_feature_mask(self.seed, block, kind, like.shape[0], like.shape[1], self.p)).to(like.dtype)
+        return torch.from_numpy(philox.dropout_feature_mask(self.seed, block, kind, like.shape[0], like.shape[1], self.p)).to(like.device,
+                                                                                                                              like.dtype)
 
 
 def attention_aggregate(q_dst, k_e, v_e, dst, n_dst, heads=8, attn_keep=None):
@@ -178,7 +181,7 @@ def local_encoder(P, cfg, batch, rot, noise, enc_sched, want_intermediates=False
     # ENC:68-71 lane feature = last valid point - first point
     lane_len = (1 - batch["lane_paddings"]).sum(-1)
     lp = batch["lane_positions"]
-    ar = torch.arange(lp.size(0))
+    ar = torch.arange(lp.size(0), device=lp.device)
     lane_feat = lp[ar, (lane_len - 1).long()] - lp[ar, 0]
 
     # ENC:73-74,103 source mask, extended by the fake copies of the target agents
@@ -189,9 +192,9 @@ def local_encoder(P, cfg, batch, rot, noise, enc_sched, want_intermediates=False
     to_agent = torch.isin(ei[1], agent_index)
     _, inv = torch.unique(ei[1][to_agent], return_inverse=True)
     ei_ext = torch.cat((ei, torch.stack((ei[0][to_agent], inv + N))), dim=-1)
-    z_fake = noise.fake_agent((A, H, 2))
+    z_fake = noise.fake_agent((A, H, 2)).to(x.device)
     x_ext = torch.cat((x, x[agent_index] + 2 * z_fake), 0)
-    orig = torch.cat((torch.arange(N), agent_index))
+    orig = torch.cat((torch.arange(N, device=x.device), agent_index))
     pad_ext = pad[orig]
     valid = ~pad_ext[:, :ref_time + 1]                      # [Nt, 21]
     pos_ext = pos[orig]
@@ -235,7 +238,7 @@ def local_encoder(P, cfg, batch, rot, noise, enc_sched, want_intermediates=False
 
     # ENC:128-182 latent SDE + GRU recurrence, iteration idx consumes history step t = 20 - idx
     h = P[pre + ".hidden"].unsqueeze(0).repeat(Nt, 1)
-    sel = torch.cat((agent_index, torch.arange(N, Nt)))     # ENC:101 new_agent_index
+    sel = torch.cat((agent_index, torch.arange(N, Nt, device=x.device)))     # ENC:101 new_agent_index
     latent, diffs = [], []
     lf = pre + ".lsde_func"
     for idx in range(H):
@@ -245,9 +248,9 @@ def local_encoder(P, cfg, batch, rot, noise, enc_sched, want_intermediates=False
         g = h.new_empty(Nt, D)
         g[nus_mask] = diffusion(P, lf + ".g_nus", h[nus_mask], s_t, c_t).repeat(1, D)      # ENC:470-482
         g[~nus_mask] = diffusion(P, lf + ".g_argo", h[~nus_mask], s_t, c_t).repeat(1, D)
-        dW = noise.encoder(idx, (Nt, D)) * float(enc_sched.sqrt_h[idx])
+        dW = noise.encoder(idx, (Nt, D)).to(h.device) * float(enc_sched.sqrt_h[idx])
         # Euler_private.step SDEINT:477-485: y1 = y0 + f*dt + g*dW (one step per interval, App. D)
-        h_ode = h + f * torch.tensor(enc_sched.dt[idx]) + g * dW
+        h_ode = h + f * torch.tensor(enc_sched.dt[idx], device=h.device) + g * dW
         h = gru_unit(P, pre + ".gru_unit", h_ode, aa_out[t], valid[:, t])
         latent.append(h)
         diffs.append(g[sel])
@@ -258,8 +261,8 @@ def local_encoder(P, cfg, batch, rot, noise, enc_sched, want_intermediates=False
 
     # ENC:187-196 pick the state of the iteration that processed each actor's first valid step
     eos = ref_time - torch.argmax(batch["bos_mask"].float(), dim=1)
-    out = latent[eos, torch.arange(N)]
-    diff_pick = diffs[eos[agent_index].repeat(2), torch.arange(2 * A)]
+    out = latent[eos, torch.arange(N, device=x.device)]
+    diff_pick = diffs[eos[agent_index].repeat(2), torch.arange(2 * A, device=x.device)]
     diff_in, diff_out = torch.chunk(diff_pick, 2, 0)
 
     # ENC:198-200 + ALEncoder ENC:732-797 (bipartite lane -> actor)
@@ -288,7 +291,7 @@ def local_encoder_ood(P, cfg, batch, rot, noise, enc_sched, eval_iter=10):
     N = x.shape[0]
     lane_len = (1 - batch["lane_paddings"]).sum(-1)
     lp = batch["lane_positions"]
-    ar = torch.arange(lp.size(0))
+    ar = torch.arange(lp.size(0), device=lp.device)
     lane_feat = lp[ar, (lane_len - 1).long()] - lp[ar, 0]
     nus_mask = batch["source"][batch["batch"]] == 0                        # ENC:211-212
     valid = ~pad[:, :ref_time + 1]
@@ -328,11 +331,11 @@ def local_encoder_ood(P, cfg, batch, rot, noise, enc_sched, eval_iter=10):
             g = h.new_empty(N, D)
             g[nus_mask] = diffusion(P, lf + ".g_nus", h[nus_mask], s_t, c_t).repeat(1, D)
             g[~nus_mask] = diffusion(P, lf + ".g_argo", h[~nus_mask], s_t, c_t).repeat(1, D)
-            dW = noise.encoder(j * H + idx, (N, D)) * float(enc_sched.sqrt_h[idx])
-            h_ode = h + f * torch.tensor(enc_sched.dt[idx]) + g * dW
+            dW = noise.encoder(j * H + idx, (N, D)).to(h.device) * float(enc_sched.sqrt_h[idx])
+            h_ode = h + f * torch.tensor(enc_sched.dt[idx], device=h.device) + g * dW
             h = gru_unit(P, pre + ".gru_unit", h_ode, aa_out[t], valid[:, t])
             latent.append(h)
-        outs.append(torch.stack(latent)[eos, torch.arange(N)])
+        outs.append(torch.stack(latent)[eos, torch.arange(N, device=x.device)])
     outs = torch.stack(outs)
     actors_std = outs.std(0).mean(-1)                                       # ENC:312
     out = outs.mean(0)
@@ -396,11 +399,11 @@ def sde_decoder(P, cfg, batch, local_embed, global_embed, noise, dec_sched, want
         s_t, c_t = float(dec_sched.sin_t0[k]), float(dec_sched.cos_t0[k])
         f = drift(P, lf + ".f_func", y, s_t, c_t)
         g = diffusion(P, lf + ".g_func", y, s_t, c_t).repeat(1, D)          # DEC:194
-        dW = noise.decoder(k, (K * N, D)) * float(dec_sched.sqrt_h[k])
+        dW = noise.decoder(k, (K * N, D)).to(y.device) * float(dec_sched.sqrt_h[k])
         prev = y
-        y = y + f * torch.tensor(dec_sched.dt[k]) + g * dW
+        y = y + f * torch.tensor(dec_sched.dt[k], device=y.device) + g * dW
         while o < dec_sched.n_out and dec_sched.out_step[o] == k + 1:
-            sol.append(torch.tensor(dec_sched.out_w0[o]) * prev + torch.tensor(dec_sched.out_w1[o]) * y)
+            sol.append(torch.tensor(dec_sched.out_w0[o], device=y.device) * prev + torch.tensor(dec_sched.out_w1[o], device=y.device) * y)
             o += 1
     sol = torch.stack(sol).permute(1, 0, 2)                                     # [K*N, T, 64]
     pi = _lin(P, pre + ".pi.3", F.relu(_ln(P, pre + ".pi.1", _lin(P, pre + ".pi.0", torch.cat((loc_exp, global_embed), -1)))))
@@ -437,7 +440,8 @@ class InjectedNoise:
 
 
 class PhiloxNoise:
-    """The host twin of the in-kernel Philox stream (trajsde_amd/philox.py); rows are global ids."""
+    """The host twin of the in-kernel Philox stream (trajsde_amd/philox.py); rows are global ids.  Returns host tensors: the
+    stages move them to the device of their state."""
 
     def __init__(self, seed, enc_row_ids=None, dec_row_ids=None, fake_row_ids=None):
         self.seed, self.enc_rows, self.dec_rows, self.fake_rows = seed, enc_row_ids, dec_row_ids, fake_row_ids
@@ -473,7 +477,8 @@ def flat_cfg(cfg):
 @torch.no_grad()
 def forward(P: Dict[str, torch.Tensor], cfg: dict, batch, noise, want_intermediates: bool = False,
             schedules: Optional[tuple] = None, ood: bool = False, drop=None):
-    """PredictionModelSDENet.forward, MODEL:74-102 (fp32, CPU).  `drop`: PhiloxDropout for train mode, None for eval."""
+    """PredictionModelSDENet.forward, MODEL:74-102 (in the dtype and on the device of `P` and `batch`).  `drop`: PhiloxDropout for
+    train mode, None for eval."""
     from trajsde_amd.schedule import decoder_schedule, encoder_schedule
     c = flat_cfg(cfg) if "encoder" in cfg else cfg
     if schedules is None:

@@ -24,11 +24,11 @@ def temporal_masks(drop, layer, n_actors, heads, like):
     (GENC:262-283) -- from the host twin of csrc/dropout.hpp: block 16 + layer, node sites on the token row n * S + s"""
     from trajsde_amd import philox
     S, block = 22, philox.TEMPORAL_BLOCK0 + layer
-    att = torch.from_numpy(philox.dropout_temporal_attn_mask(drop.seed, block, n_actors, heads, drop.p, S)).to(like.dtype)
+    att = torch.from_numpy(philox.dropout_temporal_attn_mask(drop.seed, block, n_actors, heads, drop.p, S)).to(like.device, like.dtype)
 
     def rows(kind, width):
         m = philox.dropout_feature_mask(drop.seed, block, kind, n_actors * S, width, drop.p)           # row n * S + s
-        return torch.from_numpy(m).to(like.dtype).view(n_actors, S, width).transpose(0, 1)              # -> [S, N, width]
+        return torch.from_numpy(m).to(like.device, like.dtype).view(n_actors, S, width).transpose(0, 1)  # -> [S, N, width]
     return att, rows(philox.DK_PROJ, D), rows(philox.DK_HIDDEN, 4 * D), rows(philox.DK_OUT, D)
 
 
@@ -41,7 +41,7 @@ def temporal_encoder(P, pre, x, padding_mask, heads, layers, drop=None):
     x = torch.cat((x, P[pre + ".cls_token"].expand(-1, N, -1)), 0) + P[pre + ".pos_embed"]
     S += 1
     dh = D // heads
-    causal = torch.tril(torch.ones(S, S, dtype=torch.bool))
+    causal = torch.tril(torch.ones(S, S, dtype=torch.bool, device=x.device))
     for i in range(layers):
         l = f"{pre}.transformer_encoder.layers.{i}"
         xn = _ln(P, l + ".norm1", x)
@@ -101,7 +101,7 @@ def local_encoder_grid(P, cfg, batch, rot, drop=None, inter=None):
     l_src, l_dst, lav = la[0][near], la[1][near], lav[near]
     lane_len = (1 - batch["lane_paddings"]).sum(-1)
     lp = batch["lane_positions"]
-    ar = torch.arange(lp.size(0))
+    ar = torch.arange(lp.size(0), device=lp.device)
     lane_feat = lp[ar, (lane_len - 1).long()] - lp[ar, 0]
     xn = _ln(P, l + ".norm1", out)
     r_e = rot[l_dst]

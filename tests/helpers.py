@@ -86,13 +86,16 @@ class Float64Noise:
         return self.inner.decoder(k, shape).detach().cpu().double()
 
 
-def oracle_forward64(model, cfg, batch, noise_seed=None, noise=None, want_intermediates=True, ood=False, drop=None):
+def oracle_forward64(model, cfg, batch, noise_seed=None, noise=None, want_intermediates=True, ood=False, drop=None, device="cpu"):
     """oracle_forward in float64: the parameters and the batch's floating tensors cast to double, the fp32 normals of Philox seed
-    `noise_seed` (or the restate noise source `noise`, e.g. restate.InjectedNoise) taken as they are.  Outputs are float64."""
+    `noise_seed` (or the restate noise source `noise`, e.g. restate.InjectedNoise) taken as they are.  Outputs are float64, on
+    `device` (the host by default; a GPU for whole full-size batches)."""
     import restate
-    P = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
+    P = {k: (v.detach().to(device, torch.float64) if v.is_floating_point() else v.detach().to(device).clone())
+         for k, v in model.state_dict().items()}
     src = restate.PhiloxNoise(int(noise_seed)) if noise is None else noise
-    return restate.forward(P, cfg, double_batch(batch), Float64Noise(src), want_intermediates=want_intermediates, ood=ood, drop=drop)
+    return restate.forward(P, cfg, double_batch(batch).to(device), Float64Noise(src), want_intermediates=want_intermediates, ood=ood,
+                           drop=drop)
 
 
 def trained_like_parameters(model, seed, strength=1.0):
@@ -169,7 +172,7 @@ def reference_l2(y, loc, reg_mask):
     ade = l2.clone()
     ade[:, ~reg_mask] = 0
     best = torch.argmin(ade.mean(-1), dim=0)
-    minl2 = l2[best, torch.arange(l2.size(1))]
+    minl2 = l2[best, torch.arange(l2.size(1), device=l2.device)]
     return minl2[reg_mask].mean(), best
 
 
@@ -180,7 +183,7 @@ def reference_laplace_nll(y, out_loc4, reg_mask, eps=1e-6):
     d_ = diff.clone()
     d_[:, ~reg_mask] = 0
     best = torch.argmin(d_.mean(-1), dim=0)
-    ar = torch.arange(best.size(0))
+    ar = torch.arange(best.size(0), device=best.device)
     loc, scale = loc[best, ar], scale[best, ar]
     scale = scale.clone()
     with torch.no_grad():
@@ -189,21 +192,23 @@ def reference_laplace_nll(y, out_loc4, reg_mask, eps=1e-6):
     return nll[reg_mask].mean(), best
 
 
-def oracle_full_grads(model, cfg, batch_cpu, seed, w_l2, w_diff, want_parts=False, drop=None, nll_eps=None, dt=torch.float64):
+def oracle_full_grads(model, cfg, batch_cpu, seed, w_l2, w_diff, want_parts=False, drop=None, nll_eps=None, dt=torch.float64,
+                      device="cpu"):
     """end-to-end autograd over the oracle (float64, or `dt`): encoder -> aggregator -> decoder -> w_l2 L2 (or, with `nll_eps`, the
     Laplace NLL) + w_diff DiffBCE;
-    `drop`: a restate.PhiloxDropout for train-mode dropout (the masks the HIP kernels cut from their Philox stream)"""
+    `drop`: a restate.PhiloxDropout for train-mode dropout (the masks the HIP kernels cut from their Philox stream); `device`: where
+    the oracle and its tape live (the gradients are returned there)"""
     import restate
     import torch.nn.functional as F
     from trajsde_amd.schedule import decoder_schedule, encoder_schedule
     c = restate.flat_cfg(cfg)
     es = encoder_schedule(c["historical_steps"], c["max_past_t"], c["minimum_step"])
     ds = decoder_schedule(c["future_steps"], c["max_fut_t"], c["min_stepsize"])
-    P = {k: (v.detach().cpu().to(dt) if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
+    P = {k: (v.detach().to(device, dt) if v.is_floating_point() else v.detach().to(device).clone()) for k, v in model.state_dict().items()}
     names = [k for k in P if P[k].is_floating_point()]
     for k in names:
         P[k].requires_grad_(True)
-    b = clone_batch(batch_cpu)
+    b = clone_batch(batch_cpu).to(device)
     for k in b.keys:
         if torch.is_tensor(b[k]) and b[k].is_floating_point():
             b[k] = b[k].to(dt)
@@ -423,17 +428,17 @@ class NoiseAs:
         return self.inner.decoder(k, shape).detach().cpu().to(self.dt)
 
 
-def params_as(model, dt, prefix):
-    """(P in `dt`, the names under `prefix` that require grad)"""
-    P = {k: (v.detach().cpu().to(dt) if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
+def params_as(model, dt, prefix, device="cpu"):
+    """(P in `dt` on `device`, the names under `prefix` that require grad)"""
+    P = {k: (v.detach().to(device, dt) if v.is_floating_point() else v.detach().to(device).clone()) for k, v in model.state_dict().items()}
     names = [k for k in P if k.startswith(prefix) and P[k].is_floating_point() and not k.endswith("attn_mask")]
     for k in names:
         P[k].requires_grad_(True)
     return P, names
 
 
-def batch_as(batch_cpu, dt):
-    b = clone_batch(batch_cpu).to("cpu")
+def batch_as(batch_cpu, dt, device="cpu"):
+    b = clone_batch(batch_cpu).to(device)
     for k in b.keys:
         if torch.is_tensor(b[k]) and b[k].is_floating_point():
             b[k] = b[k].to(dt)
@@ -444,21 +449,21 @@ def stage_grads(P, names, prefix):
     return {k[len(prefix):]: (P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])) for k in names}
 
 
-def oracle_decoder_grads(model, cfg, batch_cpu, local, glob, y_rot, seed, nll_eps=None, dt=torch.float64):
-    """autograd over the oracle's SDE decoder in `dt` on the given (fp32) embeddings and the fp32 Philox normals of `seed`, under the
-    L2 loss (or, with `nll_eps`, the Laplace NLL) -> (loss, best mode, {decoder param: grad}, d local_embed, d global_embed)"""
+def oracle_decoder_grads(model, cfg, batch_cpu, local, glob, y_rot, seed, nll_eps=None, dt=torch.float64, device="cpu"):
+    """autograd over the oracle's SDE decoder in `dt` on `device` on the given (fp32) embeddings and the fp32 Philox normals of `seed`,
+    under the L2 loss (or, with `nll_eps`, the Laplace NLL) -> (loss, best mode, {decoder param: grad}, d local_embed, d global_embed)"""
     import restate
     from trajsde_amd.schedule import decoder_schedule
     c = restate.flat_cfg(cfg)
-    P, names = params_as(model, dt, "decoder.")
-    lo = local.detach().cpu().to(dt).requires_grad_(True)
-    gl = glob.detach().cpu().to(dt).requires_grad_(True)
+    P, names = params_as(model, dt, "decoder.", device)
+    lo = local.detach().to(device, dt).requires_grad_(True)
+    gl = glob.detach().to(device, dt).requires_grad_(True)
     sched = decoder_schedule(c["future_steps"], c["max_fut_t"], c["min_stepsize"])
     torch.set_default_dtype(dt)
     try:
         with torch.enable_grad():
-            out = restate.sde_decoder(P, c, batch_as(batch_cpu, dt), lo, gl, NoiseAs(restate.PhiloxNoise(seed), dt), sched)
-            yr = y_rot.detach().cpu().to(dt)
+            out = restate.sde_decoder(P, c, batch_as(batch_cpu, dt, device), lo, gl, NoiseAs(restate.PhiloxNoise(seed), dt), sched)
+            yr = y_rot.detach().to(device, dt)
             if nll_eps is None:
                 loss, best = reference_l2(yr, out["loc"][..., :2], out["reg_mask"])
             else:
@@ -469,34 +474,35 @@ def oracle_decoder_grads(model, cfg, batch_cpu, local, glob, y_rot, seed, nll_ep
     return float(loss.detach()), best, stage_grads(P, names, "decoder."), lo.grad, gl.grad
 
 
-def oracle_aggregator_grads(model, cfg, batch_cpu, local, d_glob, heads=8, dt=torch.float64):
-    """autograd over the oracle's global interactor in `dt` under sum(global_embed * d_glob) -> ({aggregator param: grad}, d local)"""
+def oracle_aggregator_grads(model, cfg, batch_cpu, local, d_glob, heads=8, dt=torch.float64, device="cpu"):
+    """autograd over the oracle's global interactor in `dt` on `device` under sum(global_embed * d_glob)
+    -> ({aggregator param: grad}, d local)"""
     import restate
     c = dict(restate.flat_cfg(cfg), num_heads=heads)
-    P, names = params_as(model, dt, "aggregator.")
-    lo = local.detach().cpu().to(dt).requires_grad_(True)
-    b = batch_as(batch_cpu, dt)
+    P, names = params_as(model, dt, "aggregator.", device)
+    lo = local.detach().to(device, dt).requires_grad_(True)
+    b = batch_as(batch_cpu, dt, device)
     torch.set_default_dtype(dt)
     try:
         rot, _ = restate.rotate_inputs(b)
         with torch.enable_grad():
             glob = restate.global_interactor(P, c, b, rot, lo)
-            (glob * d_glob.detach().cpu().to(dt)).sum().backward()
+            (glob * d_glob.detach().to(device, dt)).sum().backward()
     finally:
         torch.set_default_dtype(torch.float32)
     return stage_grads(P, names, "aggregator."), lo.grad
 
 
-def oracle_encoder_grads(model, cfg, batch_cpu, d_local, seed, diff_weight, dt=torch.float64):
-    """autograd over the oracle's SDE local encoder in `dt` under sum(local_embed * d_local) + diff_weight * DiffBCE
+def oracle_encoder_grads(model, cfg, batch_cpu, d_local, seed, diff_weight, dt=torch.float64, device="cpu"):
+    """autograd over the oracle's SDE local encoder in `dt` on `device` under sum(local_embed * d_local) + diff_weight * DiffBCE
     -> ({encoder param: grad}, DiffBCE, d aa_out)"""
     import restate
     import torch.nn.functional as F
     from trajsde_amd.schedule import encoder_schedule
     c = restate.flat_cfg(cfg)
     sched = encoder_schedule(c["historical_steps"], c["max_past_t"], c["minimum_step"])
-    P, names = params_as(model, dt, "encoder.")
-    b = batch_as(batch_cpu, dt)
+    P, names = params_as(model, dt, "encoder.", device)
+    b = batch_as(batch_cpu, dt, device)
     torch.set_default_dtype(dt)
     try:
         rot, _ = restate.rotate_inputs(b)
@@ -505,7 +511,7 @@ def oracle_encoder_grads(model, cfg, batch_cpu, d_local, seed, diff_weight, dt=t
             inter["aa_out"].retain_grad()
             bce = (F.binary_cross_entropy(diff_in, torch.zeros_like(diff_in)) +
                    F.binary_cross_entropy(diff_out, torch.ones_like(diff_out)))
-            ((local * d_local.detach().cpu().to(dt)).sum() + diff_weight * bce).backward()
+            ((local * d_local.detach().to(device, dt)).sum() + diff_weight * bce).backward()
     finally:
         torch.set_default_dtype(torch.float32)
     return stage_grads(P, names, "encoder."), float(bce.detach()), inter["aa_out"].grad

@@ -326,8 +326,9 @@ _oracle_full_grads = H.oracle_full_grads
 
 
 def test_full_size_training_step_agrees_between_kernel_forms(dev):
-    """BASELINE configs[1] (64 scenes x 128 agents: 3.4 M agent-agent edges, 4.55 M embedding rows) is far beyond what the float64 oracle
-    can differentiate, so the full-size check is a cross-check: the same training step in two child processes, once with this round's
+    """BASELINE configs[1] (64 scenes x 128 agents: 3.4 M agent-agent edges, 4.55 M embedding rows): a cross-check of the kernel forms
+    with each other (the whole batch against float64 autograd over the oracle on the GPU is test_gpu_full_size_oracle.py's
+    test_full_size_training_step_matches_float64_gpu_oracle): the same training step in two child processes, once with this round's
     kernel forms (k_wgrad6 on block-scaled 16-bit products, deferred sums, the cooperative recurrence kernels) and once with the forms
     they replaced (exact fp32 weight-gradient products, one reduction per batch, one tile per wave, the encoders' attention backward on the
     vector pipe, the edge embedding's three weight-gradient problems apart, the decoder's replay and reverse sweep one wave a tile:

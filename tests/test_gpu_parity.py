@@ -201,9 +201,10 @@ def _scene_of(big, s, n, L):
 
 
 def _full_size_properties(dev, name, scenes, oracle_scenes=None, seed=4242):
-    """A BASELINE shape at full size, where the oracle is too slow to run whole: (1) outputs are finite, scales > min_scale,
-    shapes as MODEL:74-102 returns them; (2) scene independence: a scene taken out of the big batch and run alone (same
-    global Philox row ids) gives the same trajectories (<= 1e-5); (3) that scene alone matches the oracle (<= 1e-4).
+    """A BASELINE shape at full size, at the initial weights: (1) outputs are finite, scales > min_scale, shapes as MODEL:74-102
+    returns them; (2) scene independence: a scene taken out of the big batch and run alone (same global Philox row ids) gives the
+    same trajectories (<= 1e-5); (3) that scene alone matches the CPU oracle (<= 1e-4).  The whole batch against the float64
+    oracle on the GPU, at trained-like weights too: test_gpu_full_size_oracle.py.
     Returns (model on the device, cfg, big batch on the host, the big batch's outputs)."""
     import restate
     from trajsde_amd.shard import global_noise_spec
