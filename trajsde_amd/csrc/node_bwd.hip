@@ -715,8 +715,12 @@ int edge_embed_backward(const float* img, const float* geom, const float* demb, 
                         const WgradCtx& wc, const EdgeEmbedGrads& gr, hipStream_t st, const EdgeAttnGrad* ag) {
   if (E <= 0) return TRAJSDE_OK;
   const int64_t ntiles = (E + 15) / 16;
-  const int tail_threads = 512;                            // one workgroup per CU (image + a store tile per wave: 113 / 145 KB)
-  const int lds_tail = (EdgeBwdL::WA3T + (ag ? 2 * MAT64 : 0) + (tail_threads / 64) * ROWSTAGE) * 4, lds_br = (EdgeL::WA3 + MAT64) * 4;
+  // one workgroup per CU (image + a store tile per wave: 113 / 145 KB).  The bf16x6 image is 24 KB larger: with lin_k^T | lin_v^T behind
+  // it eight store tiles would ask for 168 KB, so that build runs the attention form with four waves (151 KB)
+  const auto tail_lds = [&](int threads) { return (EdgeBwdL::WA3T + (ag ? 2 * MAT64 : 0) + (threads / 64) * ROWSTAGE) * 4; };
+  const int tail_threads = tail_lds(512) <= 160 * 1024 ? 512 : 256;
+  const int lds_tail = tail_lds(tail_threads), lds_br = (EdgeL::WA3 + MAT64) * 4;
+  static_assert((EdgeBwdL::WA3T + 2 * MAT64 + 4 * ROWSTAGE) * 4 <= 160 * 1024, "edge-embedding backward tail: image + four store tiles fit LDS");
   const int gt = vec_grid(ntiles, tail_threads, lds_tail), gb = vec_grid(ntiles, 256, lds_br);
   const int tail_waves = tail_threads / 64;
   float* vp = vpart_slab(sc.vpart, int64_t(gt) * tail_waves, 256);
