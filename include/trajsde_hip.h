@@ -77,7 +77,8 @@ typedef enum {
   TRAJSDE_STAGE_DECODER_MILSTEIN = 11, /* trajsde_decoder_forward_milstein: the DECODER table; its blob + GFunc's transposes (ABI 10) */
   TRAJSDE_STAGE_DECODER_MLP_NLL_BWD = 12, /* trajsde_mlp_decoder_nll_backward: the DECODER_MLP_BWD table followed by the scale head (ABI 10) */
   TRAJSDE_STAGE_DECODER_MILSTEIN_BWD = 13, /* trajsde_decoder_l2_backward_milstein: the DECODER_BWD table; its blob + GFunc's tangent images (ABI 10) */
-  TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD = 14 /* trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; its blob + the same (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD = 14, /* trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; its blob + the same (ABI 10) */
+  TRAJSDE_STAGE_DECODER_COT_BWD = 15 /* trajsde_hip_cotangent.h: the DECODER_NLL_BWD table followed by the pi head (ABI 10) */
 } trajsde_stage;
 
 int trajsde_param_count(int stage, int num_layers /*aggregator*/, int num_modes);
@@ -376,7 +377,7 @@ int trajsde_encoder_grid_backward_train(const trajsde_batch* b, const trajsde_gr
  *      paths are replayed and differentiated through every Euler-Maruyama step.  `grads[i]` is a buffer shaped
  *      like parameter trajsde_param_name(TRAJSDE_STAGE_DECODER_BWD, i) and is overwritten; `blob_bwd` is that
  *      stage's packed image, `blob_fwd` the TRAJSDE_STAGE_DECODER one.  The pi and scale heads get no gradient
- *      from this loss.  best_mode may be null. */
+ *      from this loss (trajsde_hip_cotangent.h trains them).  best_mode may be null. */
 int64_t trajsde_decoder_backward_ws_bytes(int32_t N, int num_modes, int future_steps, int n_euler);
 int trajsde_decoder_l2_backward(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
                                 const float* local_embed /*[N,64]*/, const float* global_embed /*[K,N,64]*/,
@@ -415,6 +416,9 @@ int trajsde_decoder_nll_backward_milstein(int32_t N, int num_modes, int future_s
                                           const uint8_t* reg_mask, float eps, float min_scale, void* ws, int64_t ws_bytes, float* loss,
                                           int32_t* best_mode, float* const* grads, int n_grads, float* d_local, float* d_global,
                                           void* stream);
+
+/* The decoder stage's backward from caller-supplied cotangents of loc and pi (all K modes; trains the scale and pi heads) is declared
+ * in trajsde_hip_cotangent.h, which includes this header; its weight image is TRAJSDE_STAGE_DECODER_COT_BWD. */
 
 /* ---- backward of the aggregator stage (AGG:38-58, 92-135): dL/d global_embed -> dL/d local_embed (overwritten;
  *      the caller adds the decoder's own d local_embed) and one gradient per aggregator parameter, grads[i] shaped

@@ -17,6 +17,7 @@ STAGE_DECODER_MILSTEIN = 11   # trajsde_decoder_forward_milstein: the decoder bl
 STAGE_DECODER_MLP_NLL_BWD = 12   # trajsde_mlp_decoder_nll_backward: the MLP decoder's L2 table + the scale head (added at ABI 10)
 STAGE_DECODER_MILSTEIN_BWD = 13      # trajsde_decoder_l2_backward_milstein: the DECODER_BWD table; + GFunc's tangent images (ABI 10)
 STAGE_DECODER_MILSTEIN_NLL_BWD = 14  # trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; + the same (ABI 10)
+STAGE_DECODER_COT_BWD = 15           # trajsde_decoder_cotangent_backward: the DECODER_NLL_BWD table followed by the pi head (ABI 10)
 
 
 ABI_VERSION = 10         # trajsde_graph grew aa_src / la_lane (2); trajsde_dropout arguments (3); training tapes (4);
@@ -155,6 +156,13 @@ SIGNATURES = {
     "trajsde_sde_step": (C.c_int, [I32, P, P, P, C.POINTER(F32), C.c_int, C.POINTER(Noise), P]),
 }
 
+# include/trajsde_hip_cotangent.h: the extension header's entry points, bound like the ones above
+EXT_SIGNATURES = {
+    "trajsde_decoder_cotangent_backward_ws_bytes": (I64, [I32, C.c_int, C.c_int, C.c_int]),
+    "trajsde_decoder_cotangent_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, C.POINTER(Noise), P, F32, P, P, P, I64,
+                                                     C.POINTER(P), C.c_int, P, P, P]),
+}
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -167,7 +175,7 @@ def lib() -> C.CDLL:
         # ends up with two HIP runtimes and ours reports "no ROCm-capable device".
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

@@ -63,6 +63,18 @@ __global__ void k_init_sel(const float* img, const float* local, const float* gl
 __global__ void k_dec_init_bwd(const float* img, const float* local, const float* gsel, const float* DY0, const int32_t* best, int N,
                                float* DA, float* d_local, float* d_global, float* vpart);
 
+// ---- backward from caller-supplied cotangents of loc and pi, all K * N paths (decoder_cot_bwd.hip)
+// per-wave vector slots of k_head_bwd_cot: the loc head's LayerNorm / last-layer gradients, then the scale head's
+struct CotHeadV { enum : int { DGAM = 0, DBET = 64, DW3X = 128, DW3Y = 192, DB3 = 256, HEAD = 264, LOC = 0, SCALE = HEAD, SIZE = 2 * HEAD }; };
+struct PiV { enum : int { DGAM = 0, DBET = 64, DW3 = 128, DB3 = 192, SIZE = 196 }; };      // ... of k_pi_head_bwd
+__global__ void k_init_all(const float* img, const float* local, const float* global, int N, int K, float* y0);
+__global__ void k_head_bwd_cot(const float* img_loc, const float* img_sc, const float* states, const float* out_tab, const float* loc,
+                               const float* d_loc, float min_scale, int NN, int T, float* S_in, float* DU, float* DU2, float* DS, float* vpart);
+__global__ void k_dec_init_bwd_all(const float* img, const float* local, const float* global, const float* DY0, int N, int K, float* DA,
+                                   float* DAS, float* d_local, float* d_global, float* vpart);
+__global__ void k_pi_head_bwd(const float* img, const float* local, const float* global, const float* d_pi, int N, int K, float* DP,
+                              float* DPS, float* d_local, float* d_global, float* vpart);
+
 struct WgradCtx {
   hipStream_t st;
   float *part, *cs;            // scratch for `cap` partials of 4096 / 64 floats

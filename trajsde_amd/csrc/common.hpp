@@ -8,7 +8,7 @@
 #include <cstdio>
 #include <string>
 
-#include "../../include/trajsde_hip.h"
+#include "../../include/trajsde_hip_cotangent.h"
 
 namespace tsde {
 

@@ -15,6 +15,8 @@
 //   k_dec_init_bwd             aggr_embed backward: d local_embed, d global_embed, saves (input, da)
 //   k_wgrad / k_reduce_partials   dW = sum_rows delta^T a  as MFMA outer products over saved rows (deterministic
 //                              two-stage reduction), bias = column sums, time-feature columns = step-weighted sums
+// trajsde_decoder_cotangent_backward (host side at the end of this file, its own kernels in decoder_cot_bwd.hip) runs the replay and the
+// sweep over ALL K * N paths from caller-supplied dL/dloc and dL/dpi: no loss inside, scale and pi heads included.
 // `method: milstein` (trajsde_decoder_*_backward_milstein) runs the same host code with the replay and the sweep of
 // decoder_mil_bwd.hip (the Milstein step and its gdg term) and two more weight-gradient products.
 //
@@ -1448,7 +1450,9 @@ namespace {
 enum GradSlot {
   F0W = 0, F2W, F4W, G0W, G2W, G4W, D0W, D0B, D1W, D1B, D3W, D3B, A0W, A0B, A1W, A1B, F0B, F2B, F4B, G0B, G2B, G4B, N_GRADS,
   // TRAJSDE_STAGE_DECODER_NLL_BWD: the same table followed by the scale head (pack.hip recipe_decoder_nll_bwd)
-  S0W = N_GRADS, S0B, S1W, S1B, S3W, S3B, N_GRADS_NLL
+  S0W = N_GRADS, S0B, S1W, S1B, S3W, S3B, N_GRADS_NLL,
+  // TRAJSDE_STAGE_DECODER_COT_BWD: the NLL table followed by the pi head (pack.hip recipe_decoder_cot_bwd)
+  P0W = N_GRADS_NLL, P0B, P1W, P1B, P3W, P3B, N_GRADS_COT
 };
 constexpr int BWD_THREADS = 128;
 
@@ -1509,6 +1513,26 @@ BwdWs carve_bwd(void* ws, int64_t ws_bytes, int N, int T, int n_euler, bool& ok,
   return w;
 }
 
+// trajsde_decoder_cotangent_backward: the Laplace NLL workspace over a row domain of K * N (every path is replayed and swept), then the
+// pi head's delta rows and the two mode sums of delta rows whose input row is the actor's local embedding
+struct CotWs {
+  BwdWs w;
+  float *DP, *DAS, *DPS;
+  int64_t bytes;
+};
+CotWs carve_cot(void* ws, int64_t ws_bytes, int N, int K, int T, int n_euler, bool& ok) {
+  CotWs c;
+  const int NN = N * K;
+  c.w = carve_bwd(ws, ws_bytes, NN, T, n_euler, ok, true);
+  Carver cv(ws ? reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(ws) + uintptr_t(c.w.bytes)) : nullptr, ws_bytes - c.w.bytes);
+  c.DP = cv.take<float>(int64_t(NN) * 64);
+  c.DAS = cv.take<float>(int64_t(N) * 64);
+  c.DPS = cv.take<float>(int64_t(N) * 64);
+  c.bytes = c.w.bytes + cv.off + 256;
+  ok = ok && cv.ok;
+  return c;
+}
+
 int bwd_grid(int ntiles) {
   const int waves = BWD_THREADS / 64;
   const int g = (ntiles + waves - 1) / waves;
@@ -1542,6 +1566,166 @@ static int decoder_backward_impl(bool nll, float eps, float min_scale, int32_t N
                                  int n_euler, const float* out_table, const trajsde_noise* noise, const float* loc, const float* y,
                                  const uint8_t* reg_mask, void* ws, int64_t ws_bytes, float* loss, int32_t* best_mode, float* const* grads,
                                  int n_grads, float* d_local, float* d_global, void* stream_, bool milstein = false);
+
+// the largest K * N * max(T, n_euler) the row indices of the kernels hold (tiles and rows are 32-bit there, offsets 64-bit)
+static bool cot_rows_ok(int32_t N, int K, int T, int n_euler) {
+  return N > 0 && K > 0 && T > 0 && n_euler > 0 && int64_t(N) * K * (T > n_euler ? T : n_euler) < (int64_t(1) << 31) - 64;
+}
+
+int64_t trajsde_decoder_cotangent_backward_ws_bytes(int32_t N, int num_modes, int future_steps, int n_euler) {
+  if (!cot_rows_ok(N, num_modes, future_steps, n_euler)) return fail(TRAJSDE_ERR_INVALID, "decoder_cotangent_backward: empty or oversized problem");
+  bool ok;
+  return carve_cot(nullptr, 0, N, num_modes, future_steps, n_euler, ok).bytes;
+}
+
+int trajsde_decoder_cotangent_backward(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
+                                       const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
+                                       const float* out_table, const trajsde_noise* noise, const float* loc, float min_scale,
+                                       const float* d_loc, const float* d_pi, void* ws, int64_t ws_bytes, float* const* grads, int n_grads,
+                                       float* d_local, float* d_global, void* stream_) {
+  TS_REQUIRE(blob_fwd && blob_bwd && local_embed && global_embed && step_table && out_table && loc && d_loc && d_pi && ws && grads &&
+                 d_local && d_global,
+             "decoder_cotangent_backward: null pointer");
+  TS_REQUIRE(cot_rows_ok(N, num_modes, future_steps, n_euler), "decoder_cotangent_backward: empty or oversized problem");
+  TS_REQUIRE(n_grads == int(N_GRADS_COT),
+             "decoder_cotangent_backward: gradient count does not match trajsde_param_count(TRAJSDE_STAGE_DECODER_COT_BWD)");
+  for (int i = 0; i < int(N_GRADS_COT); ++i) TS_REQUIRE(grads[i] != nullptr, "decoder_cotangent_backward: null gradient buffer");
+  if (state_bf16())
+    return fail(TRAJSDE_ERR_UNSUPPORTED, "decoder_cotangent_backward: trajsde_state_storage(1) is not supported (the replay keeps fp32 states)");
+  if (ws_bytes < trajsde_decoder_cotangent_backward_ws_bytes(N, num_modes, future_steps, n_euler))
+    return fail(TRAJSDE_ERR_WORKSPACE, "decoder_cotangent_backward: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  bool ok;
+  const int K = num_modes, T = future_steps, NN = N * K;
+  const CotWs cw = carve_cot(ws, ws_bytes, N, K, T, n_euler, ok);
+  const BwdWs& w = cw.w;
+  DeferredSums sums(st, w.part, w.cs, w.parts, step_table, w.varena, w.varena_floats);
+  NoiseArg na{0, nullptr, nullptr};
+  if (noise) { na.seed = noise->seed; na.z = noise->z; na.row_ids = noise->row_ids; na.seed_dev = noise->seed_dev; }
+  const int ntiles = (NN + 15) / 16, atiles = (N + 15) / 16;
+  const int waves = BWD_THREADS / 64;
+  const int64_t slab = int64_t(NN) * 64;
+
+  // ---- replay of every path: the replay and sweep kernels select path best[i] * N' + i of N' * K' -- the identity over N' = K * N, K' = 1
+  TS_HIP(hipMemsetAsync(w.best, 0, sizeof(int32_t) * NN, st));
+  const float* init_img = blob_bwd + DecBwdBlob::INIT;
+  TS_LAUNCH(k_init_all, bwd_grid(ntiles), BWD_THREADS, InitBwdL::AE_END * 4, st, init_img, local_embed, global_embed, N, K, w.states);
+#if TSDE_SPLIT_H3
+  static const bool replay_coop = []() { const char* e = getenv("TRAJSDE_REPLAY_COOP"); return !(e && e[0] == '0'); }();
+  if (replay_coop)
+    TS_LAUNCH_TAG("k_sde_replay", false, k_sde_replay_coop, ntiles < 8192 ? ntiles : 8192, 256, SDE_REPLAY_COOP_LDS_BYTES, st,
+                  blob_fwd + DecBlob::SDE6, w.best, NN, 1, n_euler, step_table, na, w.states, w.H1, w.H2, w.G1, w.G2, w.GS);
+  else
+#endif
+  TS_LAUNCH(k_sde_replay, bwd_grid(ntiles), BWD_THREADS, DecSdeL::LOC * 4, st, blob_fwd + DecBlob::SDE, w.best, NN, 1, n_euler, step_table,
+            na, w.states, w.H1, w.H2, w.G1, w.G2, w.GS);
+
+  // ---- both heads from the cotangent, one pass over the saved states
+  constexpr int64_t SHARED_VPART_FLOATS = int64_t(256) * (BWD_THREADS / 64) * 512;       // BwdWs: w.vpart
+  int head_grid = bwd_grid(ntiles * T);
+  if (int64_t(head_grid) * waves * CotHeadV::SIZE > SHARED_VPART_FLOATS) head_grid = int(SHARED_VPART_FLOATS / (waves * CotHeadV::SIZE));
+  const int head_waves = head_grid * waves;
+  float* vp = vpart_slab(w.vpart, head_waves, CotHeadV::SIZE);
+  TS_LAUNCH(k_head_bwd_cot, head_grid, BWD_THREADS, 2 * HeadBwdL::SIZE * 4, st, blob_bwd + DecBwdBlob::HEAD, blob_bwd + DecNllBwdBlob::HEAD_SC,
+            w.states, out_table, loc, d_loc, min_scale, NN, T, w.S_in, w.DU, w.DU2, w.DS, vp);
+  {
+    ColsumBatch cb(st, head_waves, CotHeadV::SIZE);
+    const float *vl = vp + CotHeadV::LOC, *vs = vp + CotHeadV::SCALE;
+    cb.add(vl + CotHeadV::DGAM, 64, grads[D1W]);
+    cb.add(vl + CotHeadV::DBET, 64, grads[D1B]);
+    cb.add(vl + CotHeadV::DW3X, 128, grads[D3W]);      // rows x, y of decoder.3.weight [2,64]
+    cb.add(vl + CotHeadV::DB3, 2, grads[D3B]);
+    cb.add(vs + CotHeadV::DGAM, 64, grads[S1W]);
+    cb.add(vs + CotHeadV::DBET, 64, grads[S1B]);
+    cb.add(vs + CotHeadV::DW3X, 128, grads[S3W]);
+    cb.add(vs + CotHeadV::DB3, 2, grads[S3B]);
+    if (int rc = cb.flush()) return rc;
+  }
+
+  // ---- reverse sweep of every path (see decoder_backward_impl for the choice between the two forms)
+  const int sweep_grid = bwd_grid(ntiles);
+#if TSDE_SPLIT_H3
+  static const bool sweep_coop_env = []() { const char* e = getenv("TRAJSDE_SWEEP_COOP"); return !(e && e[0] == '0'); }();
+  bool sweep_coop = sweep_coop_env;
+#else
+  bool sweep_coop = false;
+#endif
+  constexpr int64_t SWEEP_ROWS_MAX = SHARED_VPART_FLOATS / SweepV::SIZE < 8192 ? SHARED_VPART_FLOATS / SweepV::SIZE : 8192;
+  const int64_t coop_lds = int64_t(SDE_BWD_COOP_LDS_BYTES) + int64_t(8 * n_euler + 4 * T) * 4;
+  if (sweep_coop && coop_lds > 150 * 1024) sweep_coop = false;
+  const int sweep_rows = sweep_coop ? int(ntiles < SWEEP_ROWS_MAX ? ntiles : SWEEP_ROWS_MAX) : sweep_grid * waves;
+  vp = vpart_slab(w.vpart, sweep_rows, SweepV::SIZE);
+  if (sweep_coop) {
+    const SdeBwdCoopArgs ca{blob_bwd + DecBwdBlob::SWEEP, w.best, NN, 1, T, n_euler, step_table, out_table, na, w.H1, w.H2, w.G1, w.G2, w.GS,
+                            w.DS, w.DH1, w.DH2, w.DF, w.DG1, w.DG2, w.DY0, vp};
+    TS_LAUNCH_TAG("k_sde_bwd", false, k_sde_bwd_coop, sweep_rows, 256, int(coop_lds), st, ca);
+  } else {
+    TS_LAUNCH(k_sde_bwd, sweep_grid, BWD_THREADS, SweepL::SIZE * 4, st, blob_bwd + DecBwdBlob::SWEEP, w.best, NN, 1, T, n_euler, step_table,
+              out_table, na, w.H1, w.H2, w.G1, w.G2, w.GS, w.DS, w.DH1, w.DH2, w.DF, w.DG1, w.DG2, w.DY0, vp);
+  }
+  {
+    ColsumBatch cb(st, sweep_rows, SweepV::SIZE);
+    cb.add(vp + SweepV::DV4, 64, grads[G4W]);
+    cb.add(vp + SweepV::DC4, 1, grads[G4B]);
+    if (int rc = cb.flush()) return rc;
+  }
+
+  // ---- aggr_embed over all modes (overwrites d_local, d_global), then the pi head (adds to both)
+  const int init_grid = bwd_grid(atiles);
+  vp = vpart_slab(w.vpart, int64_t(init_grid) * waves, InitV::SIZE);
+  TS_LAUNCH(k_dec_init_bwd_all, init_grid, BWD_THREADS, InitBwdL::SIZE * 4, st, init_img, local_embed, global_embed, w.DY0, N, K, w.DA, cw.DAS,
+            d_local, d_global, vp);
+  {
+    ColsumBatch cb(st, init_grid * waves, InitV::SIZE);
+    cb.add(vp + InitV::DGAM, 64, grads[A1W]);
+    cb.add(vp + InitV::DBET, 64, grads[A1B]);
+    if (int rc = cb.flush()) return rc;
+  }
+  vp = vpart_slab(w.vpart, int64_t(init_grid) * waves, PiV::SIZE);
+  TS_LAUNCH(k_pi_head_bwd, init_grid, BWD_THREADS, PiBwdL::SIZE * 4, st, blob_bwd + DecCotBwdBlob::PI, local_embed, global_embed, d_pi, N, K,
+            cw.DP, cw.DPS, d_local, d_global, vp);
+  {
+    ColsumBatch cb(st, init_grid * waves, PiV::SIZE);
+    cb.add(vp + PiV::DGAM, 64, grads[P1W]);
+    cb.add(vp + PiV::DBET, 64, grads[P1B]);
+    cb.add(vp + PiV::DW3, 64, grads[P3W]);
+    cb.add(vp + PiV::DB3, 1, grads[P3B]);
+    if (int rc = cb.flush()) return rc;
+  }
+
+  // ---- weight gradients
+  const WgradCtx wc{st, w.part, w.cs, step_table, w.parts};
+  const int64_t RS = slab / 64 * n_euler, RT = slab / 64 * T;
+  int rc;
+  {
+    WgradBatch sde(wc, RS, NN);                             // the five SDE matrices over the same (step, path) rows
+    if ((rc = sde.add(w.DH1, 64, w.states, 64, grads[F0W], 66, 0, grads[F0B], 1))) return rc;
+    if ((rc = sde.add(w.DH2, 64, w.H1, 64, grads[F2W], 64, 0, grads[F2B], 0))) return rc;
+    if ((rc = sde.add(w.DF, 64, w.H2, 64, grads[F4W], 64, 0, grads[F4B], 0))) return rc;
+    if ((rc = sde.add(w.DG1, 64, w.states, 64, grads[G0W], 66, 0, grads[G0B], 1))) return rc;
+    if ((rc = sde.add(w.DG2, 64, w.G1, 64, grads[G2W], 64, 0, grads[G2B], 0))) return rc;
+    if ((rc = sde.flush())) return rc;
+  }
+  {
+    WgradBatch heads(wc, RT, RT);                           // the two heads' first layers over the same (output step, path) rows
+    if ((rc = heads.add(w.DU, 64, w.S_in, 64, grads[D0W], 64, 0, grads[D0B], 0))) return rc;
+    if ((rc = heads.add(w.DU2, 64, w.S_in, 64, grads[S0W], 64, 0, grads[S0B], 0))) return rc;
+    if ((rc = heads.flush())) return rc;
+  }
+  {
+    WgradBatch glob(wc, NN, NN);                            // the global halves: aggr_embed.0 = cat(global, local), pi.0 = cat(local, global)
+    if ((rc = glob.add(w.DA, 64, global_embed, 64, grads[A0W], 128, 0, grads[A0B], 0))) return rc;
+    if ((rc = glob.add(cw.DP, 64, global_embed, 64, grads[P0W], 128, 64, grads[P0B], 0))) return rc;
+    if ((rc = glob.flush())) return rc;
+  }
+  {
+    WgradBatch loc_(wc, N, N);                              // the local halves: the mode-summed delta rows against the actors' rows
+    if ((rc = loc_.add(cw.DAS, 64, local_embed, 64, grads[A0W], 128, 64, nullptr, 0))) return rc;
+    if ((rc = loc_.add(cw.DPS, 64, local_embed, 64, grads[P0W], 128, 0, nullptr, 0))) return rc;
+    if ((rc = loc_.flush())) return rc;
+  }
+  return sums.finish();
+}
 
 int trajsde_decoder_l2_backward(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
                                 const float* local_embed, const float* global_embed, const float* step_table, int n_euler,

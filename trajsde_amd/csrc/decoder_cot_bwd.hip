@@ -1,0 +1,293 @@
+// decoder_cot_bwd.hip -- kernels of trajsde_decoder_cotangent_backward (host side: decoder_bwd.hip), the SDEDecoder's backward from
+// caller-supplied cotangents dL/dloc [K,N,T,4] and dL/dpi [N,K] for gfx950.  Every one of the K * N paths carries gradient, so the
+// replay and the reverse sweep of decoder_bwd.hip / recur.hip run over a row domain of K * N with the identity selection (row
+// r = k * N + n is path r: the forward's Philox counter); what is new here is what the welded entry points fuse with their loss or
+// restrict to the winning mode:
+//
+//   k_init_all           y0 of all K * N paths                                   (aggr_embed, DEC:82; local row n = r % N)
+//   k_head_bwd_cot       loc AND scale head, forward + backward per (row, output step) in one pass over the saved states: the upstream
+//                        gradient is read from d_loc instead of formed against y; the scale channels pass through ELU + 1 + min_scale
+//   k_dec_init_bwd_all   aggr_embed backward over all modes; d local_embed = the modes' sum in mode order
+//   k_pi_head_bwd        pi head Linear(128,64) LN ReLU Linear(64,1) on [local | global] rows (DEC:93-94), forward + backward; ADDS its
+//                        input gradients to d_local / d_global
+//
+// The mode sums into d_local run inside ONE wave per 16 actors, modes 0..K-1 in order: no atomics, identical calls give identical words.
+// A separate unit so that the kernels of decoder_bwd.hip keep their listings.
+#include "common.hpp"
+#include "layouts.hpp"
+#include "tile.hpp"
+#include "tile_bwd.hpp"
+#include "bwd.hpp"
+
+namespace tsde {
+
+__global__ __launch_bounds__(128) void k_init_all(const float* __restrict__ img, const float* __restrict__ local,
+                                                  const float* __restrict__ global, int N, int K, float* __restrict__ y0) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  stage_blob(lds, img, InitBwdL::AE_END);
+  const Lane L;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  const int NN = N * K;
+  const int ntiles = (NN + 15) / 16;
+  for (int tile = blockIdx.x * waves + wave; tile < ntiles; tile += gridDim.x * waves) {
+    keep_lds_reads_here();
+    const int row = tile * 16 + L.n;
+    const int r = row < NN ? row : NN - 1;
+    f4 gl[4], lo[4], a[4];
+    load_row(gl, global, r, L.g);
+    load_row(lo, local, r % N, L.g);
+    load_vec<4>(a, lds + InitBwdL::BA, L.g);
+    linear_acc<4, 4>(a, gl, lds + InitBwdL::WA_G, L.lane);
+    linear_acc<4, 4>(a, lo, lds + InitBwdL::WA_L, L.lane);
+    layer_norm<4>(a, lds + InitBwdL::AG, lds + InitBwdL::AE, L.g);
+    relu<4>(a);
+    if (row < NN) store_row(a, y0, row, L.g);
+  }
+}
+
+// one head (image H = HeadL fields, W0T behind it) on the interpolated state s with the upstream gradient (gx, gy) of its two outputs:
+// du := gradient at the first layer's output (the weight gradient's delta row), ds += W0^T du; accumulates the head's vector gradients
+struct HeadAcc {
+  f4 dgam[4], dbet[4], dw3x[4], dw3y[4];
+  float db3x, db3y;
+};
+__device__ __forceinline__ void head_cot_pass(const float* img, const f4 (&s)[4], float gx, float gy, HeadAcc& A, f4 (&du)[4], f4 (&ds)[4],
+                                              const Lane& L) {
+  const float* H = img + HeadBwdL::FWD;
+  f4 u[4], v[4];
+  linear<4, 4>(u, s, H + HeadL::W0, H + HeadL::B0, L);
+  const float rstd = ln_normalize(u);                       // u = x_hat
+  bool pos[16];
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt) {
+    const f4 ga = *reinterpret_cast<const f4*>(H + HeadL::G + 16 * jt + 4 * L.g);
+    const f4 be = *reinterpret_cast<const f4*>(H + HeadL::E + 16 * jt + 4 * L.g);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float pre = u[jt][c] * ga[c] + be[c];
+      pos[jt * 4 + c] = pre > 0.f;
+      v[jt][c] = fmaxf(pre, 0.f);
+    }
+  }
+  A.db3x += gx;
+  A.db3y += gy;
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt) {
+    const f4 wx = *reinterpret_cast<const f4*>(H + HeadL::W3 + 16 * jt + 4 * L.g);
+    const f4 wy = *reinterpret_cast<const f4*>(H + HeadL::W3 + 64 + 16 * jt + 4 * L.g);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      A.dw3x[jt][c] = fmaf(gx, v[jt][c], A.dw3x[jt][c]);
+      A.dw3y[jt][c] = fmaf(gy, v[jt][c], A.dw3y[jt][c]);
+      du[jt][c] = pos[jt * 4 + c] ? fmaf(gx, wx[c], gy * wy[c]) : 0.f;
+    }
+  }
+  ln_backward(du, u, rstd, H + HeadL::G, L.g, A.dgam, A.dbet);
+  linear_adj<4, 4>(ds, du, img + HeadBwdL::W0T, L);
+}
+__device__ __forceinline__ void head_acc_zero(HeadAcc& A) {
+  zero4(A.dgam); zero4(A.dbet); zero4(A.dw3x); zero4(A.dw3y);
+  A.db3x = A.db3y = 0.f;
+}
+__device__ __forceinline__ void head_acc_flush(const HeadAcc& A, float* vp, const Lane& L) {
+  flush_vec(A.dgam, vp + CotHeadV::DGAM, L);
+  flush_vec(A.dbet, vp + CotHeadV::DBET, L);
+  flush_vec(A.dw3x, vp + CotHeadV::DW3X, L);
+  flush_vec(A.dw3y, vp + CotHeadV::DW3Y, L);
+  flush_scalar(A.db3x, vp + CotHeadV::DB3, L);
+  flush_scalar(A.db3y, vp + CotHeadV::DB3 + 1, L);
+}
+
+// rows are (o, r): o = output step, r = path (k * N + n) of NN = K * N.  S_in / DU / DU2 / DS are [T][NN][64]; loc / d_loc are [NN][T][4]
+__global__ __launch_bounds__(128) void k_head_bwd_cot(const float* __restrict__ img_loc, const float* __restrict__ img_sc,
+                                                      const float* __restrict__ states, const float* __restrict__ out_tab,
+                                                      const float* __restrict__ loc, const float* __restrict__ d_loc, float min_scale, int NN,
+                                                      int T, float* __restrict__ S_in, float* __restrict__ DU, float* __restrict__ DU2,
+                                                      float* __restrict__ DS, float* __restrict__ vpart) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  stage_copy(lds, img_loc, HeadBwdL::SIZE);
+  stage_copy(lds + HeadBwdL::SIZE, img_sc, HeadBwdL::SIZE);
+  __syncthreads();
+  const Lane L;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  const int tiles_per_o = (NN + 15) / 16;
+  const int ntiles = tiles_per_o * T;
+  const int64_t slab = int64_t(NN) * D;
+  HeadAcc AL, AS;
+  head_acc_zero(AL);
+  head_acc_zero(AS);
+  for (int tile = blockIdx.x * waves + wave; tile < ntiles; tile += gridDim.x * waves) {
+    keep_lds_reads_here();
+    const int o = tile / tiles_per_o;
+    const int row = (tile - o * tiles_per_o) * 16 + L.n;
+    const int i = row < NN ? row : NN - 1;
+    const int ko = int(out_tab[o * 4]);
+    const float w0 = out_tab[o * 4 + 1], w1 = out_tab[o * 4 + 2];
+    f4 g = f4{0.f, 0.f, 0.f, 0.f};
+    if (row < NN) {
+      g = *reinterpret_cast<const f4*>(d_loc + (int64_t(i) * T + o) * 4);
+      const f4 fw = *reinterpret_cast<const f4*>(loc + (int64_t(i) * T + o) * 4);
+      // scale = ELU(raw) + 1 + min_scale (DEC:97-98): d scale / d raw = 1 for raw > 0, else exp(raw) = scale - min_scale (< = 1)
+      g[2] *= fminf(1.0f, fw[2] - min_scale);
+      g[3] *= fminf(1.0f, fw[3] - min_scale);
+    }
+    f4 s[4];
+    {
+      f4 a[4], b[4];
+      load_row(a, states + (ko - 1) * slab, i, L.g);
+      load_row(b, states + ko * slab, i, L.g);
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s[jt][c] = w0 * a[jt][c] + w1 * b[jt][c];
+    }
+    f4 du[4], ds[4];
+    zero4(ds);
+    head_cot_pass(lds, s, g[0], g[1], AL, du, ds, L);
+    if (row < NN) {
+      store_row(s, S_in + o * slab, row, L.g);
+      store_row(du, DU + o * slab, row, L.g);
+    }
+    head_cot_pass(lds + HeadBwdL::SIZE, s, g[2], g[3], AS, du, ds, L);
+    if (row < NN) {
+      store_row(du, DU2 + o * slab, row, L.g);
+      store_row(ds, DS + o * slab, row, L.g);
+    }
+  }
+  float* vp = vpart + int64_t(blockIdx.x * waves + wave) * CotHeadV::SIZE;
+  head_acc_flush(AL, vp + CotHeadV::LOC, L);
+  head_acc_flush(AS, vp + CotHeadV::SCALE, L);
+}
+
+// aggr_embed backward over all modes: one wave per 16 actors walks the modes in order.  DY0 / DA / d_global are [K][N][64]; DAS [N][64] is
+// the modes' sum of DA (the delta rows of the weight's local half, whose input row does not depend on the mode)
+__global__ __launch_bounds__(128) void k_dec_init_bwd_all(const float* __restrict__ img, const float* __restrict__ local,
+                                                          const float* __restrict__ global, const float* __restrict__ DY0, int N, int K,
+                                                          float* __restrict__ DA, float* __restrict__ DAS, float* __restrict__ d_local,
+                                                          float* __restrict__ d_global, float* __restrict__ vpart) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  stage_blob(lds, img, InitBwdL::SIZE);
+  const Lane L;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  const int ntiles = (N + 15) / 16;
+  f4 dgam[4], dbet[4];
+  zero4(dgam); zero4(dbet);
+  for (int tile = blockIdx.x * waves + wave; tile < ntiles; tile += gridDim.x * waves) {
+    const int row = tile * 16 + L.n;
+    const int i = row < N ? row : N - 1;
+    f4 lo[4], das[4];
+    load_row(lo, local, i, L.g);
+    zero4(das);
+    for (int k = 0; k < K; ++k) {
+      keep_lds_reads_here();
+      const int64_t r = int64_t(k) * N + i;
+      f4 gl[4], a[4], d[4];
+      load_row(gl, global, r, L.g);
+      load_vec<4>(a, lds + InitBwdL::BA, L.g);
+      linear_acc<4, 4>(a, gl, lds + InitBwdL::WA_G, L.lane);
+      linear_acc<4, 4>(a, lo, lds + InitBwdL::WA_L, L.lane);
+      const float rstd = ln_normalize(a);
+      load_row(d, DY0, r, L.g);
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) {
+        const f4 ga = *reinterpret_cast<const f4*>(lds + InitBwdL::AG + 16 * jt + 4 * L.g);
+        const f4 be = *reinterpret_cast<const f4*>(lds + InitBwdL::AE + 16 * jt + 4 * L.g);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (!(a[jt][c] * ga[c] + be[c] > 0.f) || row >= N) d[jt][c] = 0.f;
+      }
+      ln_backward(d, a, rstd, lds + InitBwdL::AG, L.g, dgam, dbet);   // d := d a_pre
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) das[jt] += d[jt];
+      f4 t[4];
+      linear_t(t, d, lds + InitBwdL::WA_GT, L);
+      if (row < N) {
+        store_row(d, DA, r, L.g);
+        store_row(t, d_global, r, L.g);
+      }
+    }
+    f4 t[4];
+    linear_t(t, das, lds + InitBwdL::WA_LT, L);
+    if (row < N) {
+      store_row(das, DAS, row, L.g);
+      store_row(t, d_local, row, L.g);
+    }
+  }
+  float* vp = vpart + int64_t(blockIdx.x * waves + wave) * InitV::SIZE;
+  flush_vec(dgam, vp + InitV::DGAM, L);
+  flush_vec(dbet, vp + InitV::DBET, L);
+}
+
+// pi head forward + backward, after k_dec_init_bwd_all on the same stream: d_global rows and d_local rows are read, added to and written
+// back by the one wave that owns the actor.  d_pi is [N][K] (the forward's transposed layout, DEC:94); DP [K][N][64] are the delta rows
+// of pi.0's global half, DPS [N][64] their sum over the modes (the local half)
+__global__ __launch_bounds__(128) void k_pi_head_bwd(const float* __restrict__ img, const float* __restrict__ local,
+                                                     const float* __restrict__ global, const float* __restrict__ d_pi, int N, int K,
+                                                     float* __restrict__ DP, float* __restrict__ DPS, float* __restrict__ d_local,
+                                                     float* __restrict__ d_global, float* __restrict__ vpart) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  stage_blob(lds, img, PiBwdL::SIZE);
+  const Lane L;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  const int ntiles = (N + 15) / 16;
+  f4 dgam[4], dbet[4], dw3[4];
+  zero4(dgam); zero4(dbet); zero4(dw3);
+  float db3 = 0.f;
+  for (int tile = blockIdx.x * waves + wave; tile < ntiles; tile += gridDim.x * waves) {
+    const int row = tile * 16 + L.n;
+    const int i = row < N ? row : N - 1;
+    f4 lo[4], dps[4];
+    load_row(lo, local, i, L.g);
+    zero4(dps);
+    for (int k = 0; k < K; ++k) {
+      keep_lds_reads_here();
+      const int64_t r = int64_t(k) * N + i;
+      const float g = row < N ? d_pi[int64_t(i) * K + k] : 0.f;
+      f4 gl[4], a[4], d[4];
+      load_row(gl, global, r, L.g);
+      load_vec<4>(a, lds + PiBwdL::BP, L.g);
+      linear_acc<4, 4>(a, lo, lds + PiBwdL::WP_L, L.lane);
+      linear_acc<4, 4>(a, gl, lds + PiBwdL::WP_G, L.lane);
+      const float rstd = ln_normalize(a);
+      db3 += g;
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) {
+        const f4 ga = *reinterpret_cast<const f4*>(lds + PiBwdL::PG + 16 * jt + 4 * L.g);
+        const f4 be = *reinterpret_cast<const f4*>(lds + PiBwdL::PE + 16 * jt + 4 * L.g);
+        const f4 w3 = *reinterpret_cast<const f4*>(lds + PiBwdL::WP3 + 16 * jt + 4 * L.g);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float pre = a[jt][c] * ga[c] + be[c];
+          dw3[jt][c] = fmaf(g, fmaxf(pre, 0.f), dw3[jt][c]);
+          d[jt][c] = pre > 0.f ? g * w3[c] : 0.f;
+        }
+      }
+      ln_backward(d, a, rstd, lds + PiBwdL::PG, L.g, dgam, dbet);     // d := gradient at pi.0's output
+#pragma unroll
+      for (int jt = 0; jt < 4; ++jt) dps[jt] += d[jt];
+      f4 t[4];
+      if (row < N) load_row(t, d_global, r, L.g);
+      else zero4(t);
+      linear_adj<4, 4>(t, d, lds + PiBwdL::WP_GT, L);
+      if (row < N) {
+        store_row(d, DP, r, L.g);
+        store_row(t, d_global, r, L.g);
+      }
+    }
+    f4 t[4];
+    if (row < N) load_row(t, d_local, row, L.g);
+    else zero4(t);
+    linear_adj<4, 4>(t, dps, lds + PiBwdL::WP_LT, L);
+    if (row < N) {
+      store_row(dps, DPS, row, L.g);
+      store_row(t, d_local, row, L.g);
+    }
+  }
+  float* vp = vpart + int64_t(blockIdx.x * waves + wave) * PiV::SIZE;
+  flush_vec(dgam, vp + PiV::DGAM, L);
+  flush_vec(dbet, vp + PiV::DBET, L);
+  flush_vec(dw3, vp + PiV::DW3, L);
+  flush_scalar(db3, vp + PiV::DB3, L);
+}
+
+}  // namespace tsde

@@ -425,6 +425,24 @@ struct DecBwdBlob {
 struct DecNllBwdBlob {   // Laplace NLL: the L2 blob followed by the scale head's images (forward + W0 transposed)
   enum : int { HEAD_SC = DecBwdBlob::SIZE, SIZE = HEAD_SC + HeadBwdL::SIZE };
 };
+// Backward from caller-supplied cotangents (decoder_bwd.hip trajsde_decoder_cotangent_backward): the Laplace NLL blob followed by the pi
+// head's images -- Linear(128,64) on cat(local, global) (DEC:93-94) as two forward halves and their transposes, LayerNorm, Linear(64,1)
+struct PiBwdL {
+  enum : int {
+    S_END = 0,
+    TS_FIELD(WP_L, MAT64, S), TS_FIELD(WP_G, MAT64, WP_L), TS_FIELD(BP, 64, WP_G), TS_FIELD(PG, 64, BP), TS_FIELD(PE, 64, PG),
+    TS_FIELD(WP3, 64, PE), TS_FIELD(BP3, 4, WP3),
+    FWD_END = BP3_END,
+    TS_FIELD(WP_LT, MAT64, BP3), TS_FIELD(WP_GT, MAT64, WP_LT),
+    SIZE = WP_GT_END
+  };
+};
+struct DecCotBwdBlob {
+  enum : int { PI = DecNllBwdBlob::SIZE, SIZE = PI + PiBwdL::SIZE };
+};
+static_assert(DecNllBwdBlob::HEAD_SC % 4 == 0 && DecCotBwdBlob::PI % 4 == 0 && PiBwdL::SIZE * 4 <= 160 * 1024 &&
+                  2 * HeadBwdL::SIZE * 4 <= 160 * 1024,
+              "cotangent backward images: aligned, fit LDS (the two heads side by side)");
 // Milstein reverse sweep (decoder_bwd.hip sde_bwd_body<true>): the tangent pass of GFunc along the adjoint u -- W0y u, W2 h1' -- runs
 // through linear_adj on GFunc's y-columns of net.0 and net.2 UNTRANSPOSED and unscaled (the orientation linear_adj reads as W, where
 // the SweepL `*T` fields give W^T).  The TRAJSDE_STAGE_DECODER_MILSTEIN_BWD / _NLL_BWD blobs are the Euler backward blobs with this

@@ -925,6 +925,22 @@ static void recipe_decoder_nll_bwd(Packer& P) {
   P.matT("scale.0.weight", h + HeadBwdL::W0T, 64);
 }
 
+// Backward from caller-supplied cotangents of loc and pi: the Laplace NLL table and images, then the pi head's (its gradient slots
+// follow the scale head's; layouts.hpp PiBwdL)
+static void recipe_decoder_cot_bwd(Packer& P) {
+  recipe_decoder_nll_bwd(P);
+  using I = PiBwdL;
+  const int b = DecCotBwdBlob::PI;
+  P.mat("pi.0.weight", b + I::WP_L, 64, 64, 128, 0);             // cat(local, global): DEC:93-94
+  P.mat("pi.0.weight", b + I::WP_G, 64, 64, 128, 64);
+  P.vec("pi.0.bias", b + I::BP, 64);
+  P.ln("pi.1", b + I::PG, b + I::PE);
+  P.vec("pi.3.weight", b + I::WP3, 64);
+  P.vec("pi.3.bias", b + I::BP3, 1);
+  P.matT("pi.0.weight", b + I::WP_LT, 128, 0);
+  P.matT("pi.0.weight", b + I::WP_GT, 128, 64);
+}
+
 // Milstein backward (either loss): the Euler backward's table and images, then GFunc's net.0 (y-columns) and net.2 untransposed and
 // unscaled for the sweep's tangent pass (layouts.hpp TanL); the parameter table is the Euler one (both tensors are already in it)
 static void recipe_tangent(Packer& P, int t) {
@@ -1102,6 +1118,7 @@ static bool run_recipe(Packer& P, int stage, int nl, int K) {
     case TRAJSDE_STAGE_DECODER_NLL_BWD: recipe_decoder_nll_bwd(P); return true;
     case TRAJSDE_STAGE_DECODER_MILSTEIN_BWD: recipe_decoder_milstein_bwd(P); return true;
     case TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD: recipe_decoder_milstein_nll_bwd(P); return true;
+    case TRAJSDE_STAGE_DECODER_COT_BWD: recipe_decoder_cot_bwd(P); return true;
     case TRAJSDE_STAGE_AGGREGATOR_BWD: recipe_aggregator_bwd(P, nl, K); return true;
     case TRAJSDE_STAGE_ENCODER_BWD: recipe_encoder_bwd(P); return true;
     case TRAJSDE_STAGE_ENCODER_GRID: recipe_encoder_grid(P, nl); return true;
@@ -1239,6 +1256,7 @@ int64_t trajsde_blob_floats(int stage, int num_layers, int num_modes) {
     case TRAJSDE_STAGE_DECODER_NLL_BWD: return DecNllBwdBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_MILSTEIN_BWD: return DecMilBwdBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD: return DecMilNllBwdBlob::SIZE;
+    case TRAJSDE_STAGE_DECODER_COT_BWD: return DecCotBwdBlob::SIZE;
     case TRAJSDE_STAGE_AGGREGATOR_BWD: return AggBwdBlob::size(num_layers, num_modes);
     case TRAJSDE_STAGE_ENCODER_BWD: return EncBwdBlob::SIZE;
     case TRAJSDE_STAGE_ENCODER_GRID: return EncGridBlob::size(num_layers);

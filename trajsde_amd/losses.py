@@ -3,7 +3,8 @@
 outputs, real = 0, perturbed = 1).  These classes are what the YAML's `losses:` entries resolve to: they give the
 loss *values* (validation-time reporting, tests); `training_step` takes their names and weights and differentiates
 the same losses inside the HIP backward entry points (trajsde_decoder_l2_backward / trajsde_decoder_nll_backward,
-trajsde_encoder_backward).
+trajsde_encoder_backward).  A loss set beyond {L2 | LaplaceNLLLoss} (+ DiffBCE) is differentiated by torch.autograd up to `loc` and
+`pi` and by trajsde_decoder_cotangent_backward from there: every class here is then called as `loss(data, output)`.
 """
 import torch
 import torch.nn.functional as F
@@ -58,3 +59,28 @@ class LaplaceNLLLoss:
         loc, scale = loc[best, idx], scale[best, idx].clamp(min=self.eps)
         nll = torch.log(2 * scale) + torch.abs(target - loc) / scale
         return nll[reg_mask].mean()
+
+
+class SoftTargetCrossEntropyLoss:
+    """Classification loss of the mode probabilities `pi`, HiVT's recipe (no counterpart among the reference's losses/, which never
+    train `pi`): the soft target of an actor is the softmax over the K modes of minus its masked L2 distance to `y` averaged over its
+    valid steps, detached; the loss is the cross-entropy of that target against log_softmax(pi), averaged over the actors that have a
+    valid step (0 when none has).  Gradient reaches `pi` only."""
+
+    def __init__(self, reduction: str = "mean") -> None:
+        if reduction != "mean":
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        self.reduction = reduction
+
+    def __call__(self, data, output) -> torch.Tensor:
+        target = data["y"]
+        pi = output["pi"]                                                # [N, K]
+        reg_mask = output["reg_mask"]
+        with torch.no_grad():
+            loc = output["loc"][..., :2]
+            l2 = (torch.norm(loc - target.unsqueeze(0), p=2, dim=-1) * reg_mask.unsqueeze(0)).sum(-1)     # [K, N]
+            valid = reg_mask.sum(-1)                                     # [N]
+            soft = F.softmax(-l2 / valid.clamp(min=1).to(l2.dtype), dim=0).t()
+            has = (valid > 0).to(pi.dtype)
+        ce = -(soft.to(pi.dtype) * F.log_softmax(pi, dim=-1)).sum(-1)    # [N]
+        return (ce * has).sum() / has.sum().clamp(min=1)

@@ -203,12 +203,26 @@ class PredictionModelSDENet(LightningHooks):
                 return name, float(getattr(fn, "eps", 1e-6))
         return "L2", None
 
+    def _cotangent_route(self) -> bool:
+        """True when the configured loss set is not one the fused backward entry points differentiate ({L2 | LaplaceNLLLoss}
+        (+ DiffBCE)): `training_step` then evaluates every loss except DiffBCE as the torch callable it is and hands dL/dloc, dL/dpi
+        to trajsde_decoder_cotangent_backward.  A model without losses takes neither route."""
+        if not self.loss_names:
+            return False
+        weights = dict(zip(self.loss_names, self.loss_weights))
+        unknown = set(self.loss_names) - {"L2", "LaplaceNLLLoss", "DiffBCE"}
+        return bool(unknown or self._regression_loss()[0] not in weights or ("L2" in weights and "LaplaceNLLLoss" in weights))
+
     def params_with_gradient(self):
-        """the parameters the configured losses reach (everything except the decoder's pi / scale heads and unused
-        buffers-as-parameters): the reference's autograd leaves the others' `.grad` at None, so AdamW skips them"""
+        """the parameters the configured losses reach (under L2 / LaplaceNLLLoss everything except the decoder's pi / scale heads
+        and unused buffers-as-parameters: the reference's autograd leaves the others' `.grad` at None, so AdamW skips them; a loss set
+        on the cotangent route reaches `decoder.scale.*` and `decoder.pi.*` too)"""
         from trajsde_amd import _lib
         reached = set()
-        dec_stage = _lib.STAGE_DECODER_NLL_BWD if self._regression_loss()[0] == "LaplaceNLLLoss" else _lib.STAGE_DECODER_BWD
+        if self._cotangent_route():
+            dec_stage = _lib.STAGE_DECODER_COT_BWD
+        else:
+            dec_stage = _lib.STAGE_DECODER_NLL_BWD if self._regression_loss()[0] == "LaplaceNLLLoss" else _lib.STAGE_DECODER_BWD
         for stage, sid in (("encoder", _lib.STAGE_ENCODER_BWD), ("aggregator", _lib.STAGE_AGGREGATOR_BWD),
                            ("decoder", dec_stage)):
             reached |= {f"{stage}.{n}" for n in getattr(self, stage)._rt.param_names(sid)}
@@ -238,6 +252,8 @@ class PredictionModelSDENet(LightningHooks):
         else:
             dec_fwd = _lib.STAGE_DECODER
             dec_stage = _lib.STAGE_DECODER_NLL_BWD if nll else _lib.STAGE_DECODER_BWD
+            if self._cotangent_route():
+                dec_stage = _lib.STAGE_DECODER_COT_BWD
         ps = self.__dict__.get("_pack_set_obj")
         if ps is None or ps.entries[-1][1] != dec_stage:
             enc_rt, agg_rt, dec_rt = self.encoder._rt, self.aggregator._rt, self.decoder._rt
@@ -246,7 +262,52 @@ class PredictionModelSDENet(LightningHooks):
             self.__dict__["_pack_set_obj"] = ps
         return ps
 
+    def _loss_and_gradients_cotangent(self, data, noise, w_diff: float):
+        """the step of a loss set on the cotangent route: tape-keeping forward; every configured loss except DiffBCE evaluated as
+        the torch callable it is on detached `loc` / `pi` leaves; dL/dloc and dL/dpi from torch.autograd.grad; then the decoder's
+        cotangent backward, the aggregator's and the encoder's (DiffBCE stays inside the latter, through `diff_weight`)"""
+        enc_rt, agg_rt, dec_rt = self.encoder._rt, self.aggregator._rt, self.decoder._rt
+        out, local, glob, enc_tape, agg_tape = self._forward_stages(data, noise, keep_tapes=True)
+        loc = out["loc"].detach().requires_grad_(True)
+        pi = out["pi"].detach().requires_grad_(True)
+        view = dict(out)
+        view["loc"], view["pi"] = loc, pi
+        values, total = {}, None
+        with torch.enable_grad():
+            for name, fn, w in zip(self.loss_names, self.losses, self.loss_weights):
+                if name == "DiffBCE":
+                    continue
+                v = fn(data, view)
+                values[name] = v.detach()
+                total = v * float(w) if total is None else total + v * float(w)
+            d_loc = d_pi = None
+            if total is not None and total.requires_grad:
+                d_loc, d_pi = torch.autograd.grad(total, [loc, pi], allow_unused=True)
+        dec = dec_rt.decoder_cotangent_backward(data, local, glob, out, noise, d_loc, d_pi)
+        agg = agg_rt.aggregator_backward(data, local, dec["d_global_embed"], noise, tape=agg_tape)
+        del agg_tape
+        gs = GradSet()
+        gs.add("decoder.", dec["grads"])
+        gs.add("aggregator.", agg["grads"])
+        sink = getattr(self, "_grad_sink", None)
+        if sink is not None and getattr(sink, "early_enabled", False) and self._direct_accumulation():
+            if not (hasattr(sink, "early_reduce_bundles") and sink.early_reduce_bundles(gs.bundles)):
+                early = gs.by_name()
+                named = dict(self.named_parameters())
+                sink.early_reduce([named[n] for n in early], [early[n] for n in early])
+        enc = enc_rt.encoder_backward(data, dec["d_local_embed"] + agg["d_local_embed"], noise, diff_weight=w_diff, tape=enc_tape)
+        del enc_tape
+        gs.add("encoder.", enc["grads"])
+        self.last_output = out
+        self.last_losses = dict(values)
+        if "DiffBCE" in self.loss_names:
+            self.last_losses["DiffBCE"] = enc["diff_loss"].detach() / w_diff if w_diff else None
+        value = enc["diff_loss"] if total is None else total.detach() + enc["diff_loss"]
+        return value.clone(), gs
+
     def _loss_and_gradients_pinned(self, data, noise, w_l2: float, w_diff: float):
+        if self._cotangent_route():
+            return self._loss_and_gradients_cotangent(data, noise, w_diff)
         enc_rt, agg_rt, dec_rt = self.encoder._rt, self.aggregator._rt, self.decoder._rt
         reg = self._regression_loss()
         # one forward per step: the encoder and aggregator run their tape-keeping forward, the backward entry points
@@ -312,10 +373,17 @@ class PredictionModelSDENet(LightningHooks):
         """MODEL:104-116: forward, the weighted sum of the configured losses, as a tensor whose `.backward()` fills
         `.grad` through the HIP backward kernels.  In train mode (`model.train()`) the stages' `dropout` is applied at the
         reference's sites (attention weights, out_proj output, the two FFN activations of every attention block) with masks
-        cut from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()` switches it off, as in the reference.  The kernels implement the
-        shipped loss set (losses/L2.py + losses/diff_BCE.py, CFG:78-83) and losses/laplace_nll_loss.py in place of L2; any other loss
-        is refused rather than silently differentiated elsewhere.  A decoder with `method: milstein` trains too (its reverse sweep
-        differentiates the gdg term: trajsde_decoder_*_backward_milstein), on the GPU only."""
+        cut from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()` switches it off, as in the reference.  The kernels fuse the
+        shipped loss set (losses/L2.py + losses/diff_BCE.py, CFG:78-83) and losses/laplace_nll_loss.py in place of L2 into the decoder
+        backward.  Any other loss set -- further `loss(data, output)` callables on `loc` / `pi`, or L2 together with LaplaceNLLLoss --
+        takes the cotangent route: the losses (DiffBCE apart) are evaluated by torch on the forward's `loc` and `pi`, and their
+        gradients dL/dloc, dL/dpi go through the HIP backward of all K modes (trajsde_decoder_cotangent_backward), which trains the
+        `pi` and `scale` heads as well.  A decoder with `method: milstein` trains under the fused sets (its reverse sweep differentiates
+        the gdg term: trajsde_decoder_*_backward_milstein), on the GPU only; the cotangent route is Euler-only."""
+        custom = self._cotangent_route()
+        if custom and getattr(self.decoder, "method", "euler") == "milstein":
+            raise NotImplementedError("`method: milstein` trains under L2 or LaplaceNLLLoss (+ DiffBCE) only: the cotangent route that "
+                                      f"differentiates {self.loss_names} is built for the Euler-Maruyama solve")
         runtime.refuse_milstein_training(self.decoder)
         if not self.rotate:
             raise NotImplementedError("rotate=False is not built (shipped config: rotate: true, CFG:18)")
@@ -326,11 +394,11 @@ class PredictionModelSDENet(LightningHooks):
             raise NotImplementedError("training with `uncertain: False` is not built: the reference's own losses chunk loc | scale out of "
                                       "FOUR channels (losses/L2.py:12); on the two-channel output they regress x against both targets")
         weights = dict(zip(self.loss_names, self.loss_weights))
-        unknown = set(self.loss_names) - {"L2", "LaplaceNLLLoss", "DiffBCE"}
         reg_name = self._regression_loss()[0]
-        if unknown or reg_name not in weights or ("L2" in weights and "LaplaceNLLLoss" in weights):
-            raise NotImplementedError("training_step differentiates ONE regression loss (L2 or LaplaceNLLLoss) + DiffBCE through the HIP "
-                                      f"kernels; configured: {self.loss_names}")
+        if not self.loss_names:
+            raise NotImplementedError("training_step needs a configured loss set (`losses` / `losses_module` / `loss_weights`)")
+        if custom:                                           # (refused before the batch is touched where the kernels cannot run)
+            runtime._require_gpu(next(self.parameters()), "model parameters (training_step)")
         if data.y is None:
             raise ValueError("training_step needs targets (data.y)")
         noise = runtime.NoiseSpec.resolve(noise)
@@ -349,7 +417,7 @@ class PredictionModelSDENet(LightningHooks):
             # enough to make the loss differentiable, and 250 fewer inputs are 250 fewer edges for the engine to walk every step
             params = [p for p in params if p.requires_grad][:1]
             self.__dict__["_one_param"] = params[0] if params else None
-        loss = _PathLoss.apply(self, data, noise, float(weights[reg_name]), float(weights.get("DiffBCE", 0.0)), *params)
+        loss = _PathLoss.apply(self, data, noise, 1.0 if custom else float(weights[reg_name]), float(weights.get("DiffBCE", 0.0)), *params)
         n_rows = int(self.last_output["loc"].size(1))
         for name in self.loss_names:                                          # MODEL:112: one entry per configured loss
             if self.last_losses.get(name) is not None:

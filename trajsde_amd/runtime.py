@@ -715,6 +715,61 @@ class StageRuntime:
                                             best.data_ptr(), arr, len(names), d_local.data_ptr(), d_global.data_ptr(), _stream()), name)
         return {"loss": loss[0], "best_mode": best, "grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
 
+    def decoder_cotangent_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
+                                   noise: NoiseSpec, d_loc: Optional[torch.Tensor], d_pi: Optional[torch.Tensor]) -> Dict[str, object]:
+        """Vector-Jacobian product of the decoder stage (DEC:77-105, Euler-Maruyama) at the forward's noise, from caller-supplied
+        cotangents: `d_loc` = dL/dloc [K,N,T,4] (or [K,N,T,2] without the scale head) and `d_pi` = dL/dpi [N,K] of ANY loss over all K
+        modes; None is zeros.  `out` = decoder_forward(...), `noise` the NoiseSpec it ran with.  Every one of the K * N paths is
+        replayed and swept in reverse, so the workspace is about K times decoder_l2_backward's.  Returns {"grads": {param name:
+        tensor} keyed by param_names(STAGE_DECODER_COT_BWD) -- `scale.*` and `pi.*` included --, "d_local_embed", "d_global_embed"}."""
+        m = self.module
+        if getattr(m, "method", "euler") == "milstein":
+            raise NotImplementedError("decoder_cotangent_backward differentiates the Euler-Maruyama solve only: `method: milstein` trains "
+                                      "under L2 or LaplaceNLLLoss (+ DiffBCE), whose backward is fused with the Milstein sweep")
+        if noise is None:
+            raise _lib.TrajsdeError("decoder_cotangent_backward needs the NoiseSpec of the forward pass (seed or z_dec)")
+        _require_gpu(local_embed, "local_embed")
+        dev = local_embed.device
+        K, T = int(m.num_modes), int(m.future_steps)
+        N = local_embed.shape[0]
+        sched, step_tab, out_tab = _TABLES.get(("dec", T, float(m.max_fut_t), float(m.min_stepsize)),
+                                               lambda: decoder_schedule(T, float(m.max_fut_t), float(m.min_stepsize)), dev)
+        loc4 = _loc4(out)
+        if d_loc is None:
+            d_loc4 = torch.zeros(K, N, T, 4, device=dev, dtype=torch.float32)
+        else:
+            if tuple(d_loc.shape) not in ((K, N, T, 4), (K, N, T, 2)):
+                raise _lib.TrajsdeError(f"d_loc must be [{K},{N},{T},4] (or ...,2 without the scale channels), got {tuple(d_loc.shape)}")
+            d_loc4 = d_loc.detach().to(device=dev, dtype=torch.float32)
+            if d_loc4.shape[-1] == 2:                       # `uncertain: False`: no scale channels came out, none carry gradient
+                d_loc4 = torch.cat([d_loc4, torch.zeros_like(d_loc4)], dim=-1)
+            d_loc4 = d_loc4.contiguous()
+        if d_pi is None:
+            d_pi_c = torch.zeros(N, K, device=dev, dtype=torch.float32)
+        else:
+            if tuple(d_pi.shape) != (N, K):
+                raise _lib.TrajsdeError(f"d_pi must be [{N},{K}], got {tuple(d_pi.shape)}")
+            d_pi_c = d_pi.detach().to(device=dev, dtype=torch.float32).contiguous()
+        L = _lib.lib()
+        stage = _lib.STAGE_DECODER_COT_BWD
+        names = self.param_names(stage)
+        grads = self._grad_buffers(stage)
+        arr, _keep = grads.pointer_array()
+        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
+        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
+        cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
+        ws_bytes = L.trajsde_decoder_cotangent_backward_ws_bytes(N, K, T, sched.n_euler)
+        if ws_bytes < 0:
+            raise _lib.TrajsdeError(f"trajsde_decoder_cotangent_backward_ws_bytes: {L.trajsde_last_error().decode()}")
+        with torch.cuda.device(dev):
+            ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+            _lib.check(L.trajsde_decoder_cotangent_backward(
+                N, K, T, self.blob().data_ptr(), self.blob(stage).data_ptr(), local_embed.contiguous().data_ptr(),
+                global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler, out_tab.data_ptr(), C.byref(cn),
+                loc4.data_ptr(), float(m.min_scale), d_loc4.data_ptr(), d_pi_c.data_ptr(), ws.data_ptr(), ws_bytes, arr, len(names),
+                d_local.data_ptr(), d_global.data_ptr(), _stream()), "trajsde_decoder_cotangent_backward")
+        return {"grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
+
     # ---------------------------------------------------------------- encoder
     def encoder_forward(self, data, noise: Optional[NoiseSpec] = None, preserve_side_effects: bool = False):
         """LocalEncoderSDESepPara2.forward (ENC:66-202) -> (local_embed, diff_in, diff_out, label_in, label_out).
