@@ -78,7 +78,8 @@ typedef enum {
   TRAJSDE_STAGE_DECODER_MLP_NLL_BWD = 12, /* trajsde_mlp_decoder_nll_backward: the DECODER_MLP_BWD table followed by the scale head (ABI 10) */
   TRAJSDE_STAGE_DECODER_MILSTEIN_BWD = 13, /* trajsde_decoder_l2_backward_milstein: the DECODER_BWD table; its blob + GFunc's tangent images (ABI 10) */
   TRAJSDE_STAGE_DECODER_MILSTEIN_NLL_BWD = 14, /* trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; its blob + the same (ABI 10) */
-  TRAJSDE_STAGE_DECODER_COT_BWD = 15 /* trajsde_hip_cotangent.h: the DECODER_NLL_BWD table followed by the pi head (ABI 10) */
+  TRAJSDE_STAGE_DECODER_COT_BWD = 15, /* trajsde_hip_cotangent.h: the DECODER_NLL_BWD table followed by the pi head (ABI 10) */
+  TRAJSDE_STAGE_DECODER_MLP_COT_BWD = 16 /* trajsde_hip_grid_cotangent.h: the DECODER_MLP_NLL_BWD table followed by the pi head; num_layers = future_steps (ABI 10) */
 } trajsde_stage;
 
 int trajsde_param_count(int stage, int num_layers /*aggregator*/, int num_modes);

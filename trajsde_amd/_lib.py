@@ -18,6 +18,7 @@ STAGE_DECODER_MLP_NLL_BWD = 12   # trajsde_mlp_decoder_nll_backward: the MLP dec
 STAGE_DECODER_MILSTEIN_BWD = 13      # trajsde_decoder_l2_backward_milstein: the DECODER_BWD table; + GFunc's tangent images (ABI 10)
 STAGE_DECODER_MILSTEIN_NLL_BWD = 14  # trajsde_decoder_nll_backward_milstein: the DECODER_NLL_BWD table; + the same (ABI 10)
 STAGE_DECODER_COT_BWD = 15           # trajsde_decoder_cotangent_backward: the DECODER_NLL_BWD table followed by the pi head (ABI 10)
+STAGE_DECODER_MLP_COT_BWD = 16       # trajsde_mlp_decoder_cotangent_backward: the DECODER_MLP_NLL_BWD table followed by the pi head (ABI 10)
 
 
 ABI_VERSION = 10         # trajsde_graph grew aa_src / la_lane (2); trajsde_dropout arguments (3); training tapes (4);
@@ -163,6 +164,13 @@ EXT_SIGNATURES = {
                                                      C.POINTER(P), C.c_int, P, P, P]),
 }
 
+# include/trajsde_hip_grid_cotangent.h: the vanilla HiVT variant's extension header (a table of its own: the two above are each pinned,
+# name by name, by the tests of the header they mirror)
+GRID_EXT_SIGNATURES = {
+    "trajsde_mlp_decoder_cotangent_backward_ws_bytes": (I64, [I32, C.c_int, C.c_int]),
+    "trajsde_mlp_decoder_cotangent_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, F32, P, P, P, I64, C.POINTER(P), C.c_int, P, P, P]),
+}
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -175,7 +183,7 @@ def lib() -> C.CDLL:
         # ends up with two HIP runtimes and ours reports "no ROCm-capable device".
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **GRID_EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/trajsde_hip_cotangent.h"
+#include "../../include/trajsde_hip_grid_cotangent.h"
 
 namespace tsde {
 

@@ -5,7 +5,7 @@
 // MLPDecoder (GDEC:47-63) + L2 (losses/L2.py:10-27) or the Laplace NLL (losses/laplace_nll_loss.py:18-47): only the winning mode
 // of each actor carries gradient, so the head and aggr_embed backward run on N rows.  Under L2 only the loc head is differentiated;
 // under the Laplace NLL the scale head too, in a launch of its own (two head images do not fit LDS together).  The pi head gets no
-// gradient from either loss.
+// gradient from either loss.  (All K modes and the pi head, from caller-supplied dL/dloc and dL/dpi: grid_cot_bwd.hip.)
 #include "attn_common.hpp"
 #include "bwd.hpp"
 #include "common.hpp"

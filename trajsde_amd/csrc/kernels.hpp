@@ -248,6 +248,14 @@ __global__ void k_sde_bwd_mil(const float* img, const float* tan_img, const int3
                               const float* GS, const float* DS, float* DH1, float* DH2, float* DF, float* DG1, float* DG2, float* DY0,
                               float* vpart, MilRows mr);
 __global__ void k_add_mil_wgrad(float* w2, float* w0, const float* m2, const float* m0);
+// vanilla HiVT variant: the MLP decoder's backward from caller-supplied cotangents of loc and pi, all K * N rows (grid_cot_bwd.hip)
+// per-wave vector slots of k_mlp_pi_bwd: (dgamma | dbeta) of pi.1 and of pi.4, d pi.6.weight, d pi.6.bias
+struct MlpPiV { enum : int { DGAM1 = 0, DBET1 = 64, DGAM4 = 128, DBET4 = 192, DW6 = 256, DB6 = 320, SIZE = 324 }; };
+template <bool SCALE>
+__global__ void k_mlp_heads_bwd_cot(const float* img, const float* out, const float* loc, const float* d_loc, float min_scale, int NN, int T,
+                                    float* H, float* DL, float* DU, float* DOUT, float* vpart, const float* DOUT_LOC);
+__global__ void k_mlp_pi_bwd(const float* img, const float* local, const float* global, const float* d_pi, int N, int K, float* DP0,
+                             float* DPS, float* H1, float* DP3, float* d_local, float* d_global, float* vpart);
 // vanilla HiVT variant (grid.hip)
 __global__ void k_tr_prep(const float* aa_out, const uint8_t* pad, const float* tok, int N, int TT, float* X);
 template <int HEADS, bool DROP>

@@ -561,6 +561,25 @@ struct MlpDecNllBwdBlob {   // Laplace NLL: the L2 blob followed by the scale he
   enum : int { HEAD_SC = MlpDecBwdBlob::SIZE, SIZE = HEAD_SC + MlpHeadBwdL::SIZE };
 };
 static_assert(MlpHeadBwdL::SIZE * 4 <= 160 * 1024 && MlpDecNllBwdBlob::HEAD_SC % 4 == 0, "MLP head backward image: fits LDS, 16-byte aligned");
+// Backward from caller-supplied cotangents (grid_cot_bwd.hip trajsde_mlp_decoder_cotangent_backward): the Laplace NLL blob followed by the
+// three-layer pi head's image -- Linear(128,64) on cat(local, global) (GDEC:37-44, 50) as two forward halves, LayerNorm, Linear(64,64),
+// LayerNorm, Linear(64,1): the forward fields in MlpInitL's order, then the transposes the backward multiplies by
+struct MlpPiBwdL {
+  enum : int {
+    S_END = 0,
+    TS_FIELD(WP_L, MAT64, S), TS_FIELD(WP_G, MAT64, WP_L), TS_FIELD(BP, 64, WP_G), TS_FIELD(PG, 64, BP), TS_FIELD(PE, 64, PG),
+    TS_FIELD(WP3, MAT64, PE), TS_FIELD(BP3, 64, WP3), TS_FIELD(PG4, 64, BP3), TS_FIELD(PE4, 64, PG4),
+    TS_FIELD(WP6, 64, PE4), TS_FIELD(BP6, 4, WP6),
+    FWD_END = BP6_END,
+    TS_FIELD(WP3T, MAT64, BP6), TS_FIELD(WP_LT, MAT64, WP3T), TS_FIELD(WP_GT, MAT64, WP_LT),
+    SIZE = WP_GT_END
+  };
+};
+struct MlpDecCotBwdBlob {
+  enum : int { PI = MlpDecNllBwdBlob::SIZE, SIZE = PI + MlpPiBwdL::SIZE };
+};
+static_assert(MlpPiBwdL::SIZE * 4 <= 160 * 1024 && MlpDecCotBwdBlob::PI % 4 == 0 && MlpPiBwdL::WP3T % 4 == 0,
+              "MLP pi head backward image: fits LDS, 16-byte aligned");
 static_assert(SweepL::SIZE * 4 <= 160 * 1024, "sweep image must fit LDS");
 static_assert(DecBwdBlob::HEAD % 4 == 0 && DecBwdBlob::INIT % 4 == 0, "16-byte aligned images");
 

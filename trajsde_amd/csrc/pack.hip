@@ -896,6 +896,24 @@ static void recipe_decoder_mlp_nll_bwd(Packer& P, int T) {
   recipe_decoder_mlp_bwd(P, T);
   recipe_mlp_head_bwd(P, "scale", MlpDecNllBwdBlob::HEAD_SC, T);
 }
+// Backward from caller-supplied cotangents of loc and pi: the Laplace NLL table and images, then the three-layer pi head's (its
+// gradient slots follow the scale head's; layouts.hpp MlpPiBwdL)
+static void recipe_decoder_mlp_cot_bwd(Packer& P, int T) {
+  recipe_decoder_mlp_nll_bwd(P, T);
+  using I = MlpPiBwdL;
+  const int b = MlpDecCotBwdBlob::PI;
+  P.mat("pi.0.weight", b + I::WP_L, 64, 64, 128, 0);             // cat(local, global): GDEC:50
+  P.mat("pi.0.weight", b + I::WP_G, 64, 64, 128, 64);
+  P.vec("pi.0.bias", b + I::BP, 64);
+  P.ln("pi.1", b + I::PG, b + I::PE);
+  P.lin("pi.3", b + I::WP3, b + I::BP3);
+  P.ln("pi.4", b + I::PG4, b + I::PE4);
+  P.vec("pi.6.weight", b + I::WP6, 64);
+  P.vec("pi.6.bias", b + I::BP6, 1);
+  P.matT("pi.3.weight", b + I::WP3T, 64);
+  P.matT("pi.0.weight", b + I::WP_LT, 128, 0);
+  P.matT("pi.0.weight", b + I::WP_GT, 128, 64);
+}
 
 // backward images of the decoder stage (loc head, drift/diffusion nets, aggr_embed); `pi` and `scale` receive no
 // gradient from the L2 regression loss and are not packed
@@ -1125,6 +1143,7 @@ static bool run_recipe(Packer& P, int stage, int nl, int K) {
     case TRAJSDE_STAGE_DECODER_MLP: recipe_decoder_mlp(P, nl); return true;
     case TRAJSDE_STAGE_DECODER_MLP_BWD: recipe_decoder_mlp_bwd(P, nl); return true;
     case TRAJSDE_STAGE_DECODER_MLP_NLL_BWD: recipe_decoder_mlp_nll_bwd(P, nl); return true;
+    case TRAJSDE_STAGE_DECODER_MLP_COT_BWD: recipe_decoder_mlp_cot_bwd(P, nl); return true;
     case TRAJSDE_STAGE_ENCODER_GRID_BWD: recipe_encoder_grid_bwd(P, nl); return true;
   }
   return false;
@@ -1263,6 +1282,7 @@ int64_t trajsde_blob_floats(int stage, int num_layers, int num_modes) {
     case TRAJSDE_STAGE_DECODER_MLP: return MlpDecBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_MLP_BWD: return MlpDecBwdBlob::SIZE;
     case TRAJSDE_STAGE_DECODER_MLP_NLL_BWD: return MlpDecNllBwdBlob::SIZE;
+    case TRAJSDE_STAGE_DECODER_MLP_COT_BWD: return MlpDecCotBwdBlob::SIZE;
     case TRAJSDE_STAGE_ENCODER_GRID_BWD: return EncGridBwdBlob::size(num_layers);
   }
   return fail(TRAJSDE_ERR_INVALID, "unknown stage");

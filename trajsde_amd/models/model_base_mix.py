@@ -4,7 +4,9 @@ same validation / test step bookkeeping as the SDE model; the stages are the HIP
 GlobalInteractor and MLPDecoder.  Deterministic (no SDE noise).  `training_step` differentiates the shipped loss of
 this configuration (L2, configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml:62-66) or the Laplace NLL (losses/laplace_nll_loss.py,
 under which the decoder's scale head is trained too) through the HIP backward entry points (trajsde_mlp_decoder_l2_backward or
-trajsde_mlp_decoder_nll_backward -> trajsde_aggregator_backward_heads -> trajsde_encoder_grid_backward); the `ts_drop`
+trajsde_mlp_decoder_nll_backward -> trajsde_aggregator_backward_heads -> trajsde_encoder_grid_backward), or -- one of the two plus
+further `loss(data, output)` callables on `loc` / `pi`, e.g. HiVT's soft-target classification loss -- the gradients torch takes of
+the whole set with respect to `loc` and `pi` through trajsde_mlp_decoder_cotangent_backward, which trains the `pi` head too; the `ts_drop`
 augmentation (models/model_base_mix.py:95-100) masks history steps of the batch before the forward, as there.  The YAML's
 `nodecay` flag is stored and, as in the reference (no code reads it), has no effect: AdamW runs over all parameters.
 """
@@ -48,6 +50,47 @@ class _GridPathLoss(torch.autograd.Function):
         have = [x for x in ctx.grads if x is not None]
         scaled = iter(torch._foreach_mul(have, g * ctx.w))
         return (None, None, None, None) + tuple(None if x is None else next(scaled) for x in ctx.grads)
+
+
+class _GridCotangentLoss(torch.autograd.Function):
+    """sum_i w_i * loss_i of a loss set on the cotangent route as one autograd node over the parameters: every configured loss is
+    evaluated by torch on detached `loc` / `pi` leaves, torch.autograd.grad gives dL/dloc and dL/dpi, and the three HIP backward
+    entry points carry them to the parameters (see model_base_mix_sde._PathLoss's custom branch)"""
+
+    @staticmethod
+    def forward(ctx, model, data, noise, *params):
+        with torch.no_grad():
+            out = model(data, noise=noise)
+            local, glob = out["local_embed"], out["global_embed"]
+            loc = out["loc"].detach().requires_grad_(True)
+            pi = out["pi"].detach().requires_grad_(True)
+            view = dict(out)
+            view["loc"], view["pi"] = loc, pi
+            values, total = {}, None
+            with torch.enable_grad():
+                for name, fn, w in zip(model.loss_names, model.losses, model.loss_weights):
+                    v = fn(data, view)
+                    values[name] = v.detach()
+                    total = v * float(w) if total is None else total + v * float(w)
+                d_loc = d_pi = None
+                if total.requires_grad:
+                    d_loc, d_pi = torch.autograd.grad(total, [loc, pi], allow_unused=True)
+            dec = model.decoder._rt.mlp_decoder_cotangent_backward(data, local, glob, out, d_loc, d_pi)
+            agg = model.aggregator._rt.aggregator_backward(data, local, dec["d_global_embed"], noise)
+            enc = model.encoder._rt.encoder_grid_backward(data, dec["d_local_embed"] + agg["d_local_embed"], noise)
+            by_name = {"decoder." + n: g for n, g in dec["grads"].items()}
+            by_name.update({"aggregator." + n: g for n, g in agg["grads"].items()})
+            by_name.update({"encoder." + n: g for n, g in enc["grads"].items()})
+            ctx.grads = [by_name.get(n) for n in model._param_names]
+            model.last_output = out
+            model.last_losses = values
+            return total.detach().clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        have = [x for x in ctx.grads if x is not None]
+        scaled = iter(torch._foreach_mul(have, g))
+        return (None, None, None) + tuple(None if x is None else next(scaled) for x in ctx.grads)
 
 
 class PredictionModel(LightningHooks):
@@ -122,12 +165,23 @@ class PredictionModel(LightningHooks):
                 return name, float(getattr(fn, "eps", 1e-6))
         return "L2", None
 
+    def _cotangent_route(self) -> bool:
+        """True for a loss set of exactly one of L2 / LaplaceNLLLoss plus one or more further `loss(data, output)` callables on
+        `loc` / `pi` (not DiffBCE: this encoder has no diffusion outputs): `training_step` then evaluates every loss as the torch
+        callable it is and hands dL/dloc, dL/dpi to trajsde_mlp_decoder_cotangent_backward"""
+        names = list(self.loss_names)
+        regression = [n for n in names if n in ("L2", "LaplaceNLLLoss")]
+        return len(regression) == 1 and len(names) > 1 and "DiffBCE" not in names
+
     def params_with_gradient(self):
-        """the parameters the configured loss reaches: everything but the decoder's pi head, and its scale head under L2 (the
-        reference's autograd leaves their `.grad` at None, so AdamW skips them)"""
+        """the parameters the configured loss set reaches: under L2 / LaplaceNLLLoss alone everything but the decoder's pi head, and
+        its scale head under L2 (the reference's autograd leaves their `.grad` at None, so AdamW skips them); a set on the cotangent
+        route reaches `decoder.scale.*` and `decoder.pi.*` too"""
         from trajsde_amd import _lib
         reached = set()
         dec_stage = _lib.STAGE_DECODER_MLP_NLL_BWD if self._regression_loss()[0] == "LaplaceNLLLoss" else _lib.STAGE_DECODER_MLP_BWD
+        if self._cotangent_route():
+            dec_stage = _lib.STAGE_DECODER_MLP_COT_BWD
         for stage, sid in (("encoder", _lib.STAGE_ENCODER_GRID_BWD), ("aggregator", _lib.STAGE_AGGREGATOR_BWD),
                            ("decoder", dec_stage)):
             reached |= {f"{stage}.{n}" for n in getattr(self, stage)._rt.param_names(sid)}
@@ -146,13 +200,22 @@ class PredictionModel(LightningHooks):
         data.padding_mask[:, :h] = data.padding_mask[:, :h] | mask
 
     def training_step(self, data, batch_idx, noise=None):
-        """models/model_base_mix.py:94-114 for ONE regression loss: the shipped L2, or LaplaceNLLLoss (losses/laplace_nll_loss.py).  In
+        """models/model_base_mix.py:94-114 for ONE regression loss: the shipped L2, or LaplaceNLLLoss (losses/laplace_nll_loss.py) --
+        alone (the loss fused into the decoder backward, the winning mode differentiated), or together with further `loss(data, output)`
+        callables on `loc` / `pi` such as losses.SoftTargetCrossEntropyLoss (the cotangent route: torch evaluates the losses on the
+        forward's `loc` / `pi`, their gradients go through the HIP backward of all K modes and of the `pi` head).  In
         train mode the stages' `dropout` (0.1 in the reference's YAML) is applied at the reference's 36 sites -- the four of every attention
         block and of every TemporalEncoder layer -- with masks cut from the Philox stream of `noise` (csrc/dropout.hpp); `model.eval()`
         switches it off."""
-        if self.loss_names not in (["L2"], ["LaplaceNLLLoss"]):
+        custom = self._cotangent_route()
+        if not custom and self.loss_names not in (["L2"], ["LaplaceNLLLoss"]):
             raise NotImplementedError("training_step differentiates ONE regression loss (L2 or LaplaceNLLLoss) through the HIP kernels; "
                                       f"configured: {self.loss_names}")
+        if custom:                                            # (refused before the batch is touched where the kernels cannot run)
+            if not getattr(self.decoder, "uncertain", True):
+                raise NotImplementedError("training with `uncertain: False` is not built: the reference's L2 regresses x against both "
+                                          "targets on a two-channel output (losses/L2.py:12)")
+            runtime._require_gpu(next(self.parameters()), "model parameters (training_step)")
         if getattr(self, "ts_drop", False):
             self.apply_ts_drop(data)
         if not getattr(self.decoder, "uncertain", True):      # (losses/L2.py:12 chunks loc | scale out of four channels: see the SDE model)
@@ -164,10 +227,13 @@ class PredictionModel(LightningHooks):
         if not hasattr(self, "_param_names"):
             self._param_names = [n for n, _ in self.named_parameters()]
         params = [p for _, p in self.named_parameters()]
-        loss = _GridPathLoss.apply(self, data, noise, float(self.loss_weights[0]), *params)
-        name = self.loss_names[0]
-        self.log_value(f"train/{name}", self.last_losses[name], prog_bar=True, on_step=True, on_epoch=True,
-                       batch_size=int(self.last_output["loc"].size(1)))          # models/model_base_mix.py:112
+        if custom:
+            loss = _GridCotangentLoss.apply(self, data, noise, *params)
+        else:
+            loss = _GridPathLoss.apply(self, data, noise, float(self.loss_weights[0]), *params)
+        n_rows = int(self.last_output["loc"].size(1))
+        for name in self.loss_names:                                             # models/model_base_mix.py:112: one entry per loss
+            self.log_value(f"train/{name}", self.last_losses[name], prog_bar=True, on_step=True, on_epoch=True, batch_size=n_rows)
         lr = self.current_lr()
         if lr is not None:
             self.log_value("lr", lr, prog_bar=False, on_step=False, on_epoch=True, batch_size=1)

@@ -1177,6 +1177,56 @@ class StageRuntime:
                            "trajsde_mlp_decoder_nll_backward")
         return {"loss": loss[0], "best_mode": best, "grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
 
+    def mlp_decoder_cotangent_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
+                                       d_loc: Optional[torch.Tensor], d_pi: Optional[torch.Tensor]) -> Dict[str, object]:
+        """Vector-Jacobian product of MLPDecoder.forward (dec_hivt_nusargo_grid.py:47-63) from caller-supplied cotangents: `d_loc` =
+        dL/dloc [K,N,T,4] and `d_pi` = dL/dpi [N,K] of ANY loss over all K modes; None is zeros.  `out` = mlp_decoder_forward(...).
+        All K * N rows are differentiated and so is the three-layer pi head.  Returns {"grads": {param name: tensor} keyed by
+        param_names(STAGE_DECODER_MLP_COT_BWD) -- `scale.*` and `pi.*` included --, "d_local_embed", "d_global_embed"}."""
+        m = self.module
+        if not getattr(m, "uncertain", True):
+            raise _lib.TrajsdeError("mlp_decoder_cotangent_backward needs the decoder's scale head: `uncertain: False` has none "
+                                    "(dec_hivt_nusargo_grid.py:31)")
+        _require_gpu(local_embed, "local_embed")
+        dev = local_embed.device
+        K, T, N = int(m.num_modes), int(m.future_steps), local_embed.shape[0]
+        if tuple(local_embed.shape) != (N, D) or tuple(global_embed.shape) != (K, N, D):
+            raise _lib.TrajsdeError(f"local_embed must be [{N},{D}] and global_embed [{K},{N},{D}], got {tuple(local_embed.shape)} and "
+                                    f"{tuple(global_embed.shape)}")
+        loc4 = _loc4(out)
+        if tuple(loc4.shape) != (K, N, T, 4):
+            raise _lib.TrajsdeError(f"out['loc'] must be [{K},{N},{T},4], got {tuple(loc4.shape)}")
+        local_c, global_c = local_embed.to(torch.float32).contiguous(), global_embed.to(torch.float32).contiguous()
+        if d_loc is None:
+            d_loc4 = torch.zeros(K, N, T, 4, device=dev, dtype=torch.float32)
+        else:
+            if tuple(d_loc.shape) != (K, N, T, 4):
+                raise _lib.TrajsdeError(f"d_loc must be [{K},{N},{T},4], got {tuple(d_loc.shape)}")
+            d_loc4 = d_loc.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if d_pi is None:
+            d_pi_c = torch.zeros(N, K, device=dev, dtype=torch.float32)
+        else:
+            if tuple(d_pi.shape) != (N, K):
+                raise _lib.TrajsdeError(f"d_pi must be [{N},{K}], got {tuple(d_pi.shape)}")
+            d_pi_c = d_pi.detach().to(device=dev, dtype=torch.float32).contiguous()
+        L = _lib.lib()
+        stage = _lib.STAGE_DECODER_MLP_COT_BWD
+        names = self.param_names(stage)
+        grads = self._grad_buffers(stage)
+        arr, _keep = grads.pointer_array()
+        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
+        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
+        ws_bytes = L.trajsde_mlp_decoder_cotangent_backward_ws_bytes(N, K, T)
+        if ws_bytes < 0:
+            raise _lib.TrajsdeError(f"trajsde_mlp_decoder_cotangent_backward_ws_bytes: {L.trajsde_last_error().decode()}")
+        with torch.cuda.device(dev):
+            ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+            _lib.check(L.trajsde_mlp_decoder_cotangent_backward(
+                N, K, T, self.blob(stage).data_ptr(), local_c.data_ptr(), global_c.data_ptr(), loc4.data_ptr(), float(m.min_scale),
+                d_loc4.data_ptr(), d_pi_c.data_ptr(), ws.data_ptr(), ws_bytes, arr, len(names), d_local.data_ptr(), d_global.data_ptr(), _stream()),
+                "trajsde_mlp_decoder_cotangent_backward")
+        return {"grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
+
 
 class GraphContext:
     """Device-side graph structures of one batch (CSR, compacted edge lists, segment pointers), built once per
