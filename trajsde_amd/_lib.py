@@ -171,6 +171,16 @@ GRID_EXT_SIGNATURES = {
     "trajsde_mlp_decoder_cotangent_backward": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, F32, P, P, P, I64, C.POINTER(P), C.c_int, P, P, P]),
 }
 
+# include/trajsde_hip_clip.h: global-norm gradient clipping in front of the flat AdamW step (csrc/clip.hip), a table of its own too
+CLIP_EXT_SIGNATURES = {
+    "trajsde_grad_norm_ws_bytes": (I64, [I64]),
+    "trajsde_grad_norm_clip": (C.c_int, [P, I64, F32, P, I64, P, P]),
+    "trajsde_adamw_step_clipped": (C.c_int, [P, P, P, P, I64, F32, F32, F32, F32, F32, C.c_int, F32, F32, P, P]),
+}
+# the reduction's geometry (csrc/clip.hip; the workspace query returns 8 bytes per workgroup, which ties these to the library):
+# a workgroup takes CLIP_WG_FLOATS consecutive elements a pass, the grid is at most CLIP_MAX_WGS workgroups and strides beyond that
+CLIP_WG_FLOATS, CLIP_MAX_WGS = 2048, 512
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -183,7 +193,7 @@ def lib() -> C.CDLL:
         # ends up with two HIP runtimes and ours reports "no ROCm-capable device".
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **GRID_EXT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

@@ -358,6 +358,26 @@ class FlatGrads:
             self.flat.div_(dist.get_world_size())
 
 
+def clip_value_of(model) -> Optional[float]:
+    """`model.gradient_clip_val`, Lightning's name for the global-norm clip (Trainer(gradient_clip_val=...), what the reference's
+    `--gradient_clip_val` sets): None or 0 -> None (off, as in Lightning), a positive number -> that number"""
+    v = getattr(model, "gradient_clip_val", None)
+    if v is None or float(v) == 0.0:
+        return None
+    v = float(v)
+    if not v > 0.0:
+        raise ValueError(f"gradient_clip_val {v!r}: a positive number, or None / 0 for no clipping")
+    return v
+
+
+@torch.no_grad()
+def torch_clip_grad_norm(params, max_norm: float) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (norm type 2) over `params` -> [norm, coefficient] on the gradients' device, the pair the flat
+    step's launches leave in `last_grad_norm`; the coefficient is formed again here as torch formed it (no host synchronisation)"""
+    norm = torch.nn.utils.clip_grad_norm_(params, max_norm)
+    return torch.stack([norm, torch.clamp(max_norm / (norm + 1e-6), max=1.0)])
+
+
 class FlatAdamW(torch.optim.AdamW):
     """torch.optim.AdamW whose step over a contiguous fp32 GPU tensor is ONE launch (trajsde_adamw_step: torch's operations in torch's
     order, its scalars formed here as torch forms them) instead of nine element-wise ones -- 2 MB of parameters make each of them ~5 us
@@ -366,12 +386,23 @@ class FlatAdamW(torch.optim.AdamW):
     "single": the single-tensor implementation (`foreach=False`).  The two differ in one operation (exp_avg_sq.sqrt() divided by
     sqrt(1 - beta2^step): a true division in the multi-tensor form, a product with the reciprocal in the other).  State (`step`,
     `exp_avg`, `exp_avg_sq`), param_groups, state_dict and the lr schedulers are torch's own; anything the launch does not cover (amsgrad,
-    maximize, capturable, a CPU tensor, another dtype) goes to torch's step unchanged."""
+    maximize, capturable, a CPU tensor, another dtype) goes to torch's step unchanged.
+    `max_grad_norm`: torch.nn.utils.clip_grad_norm_(params, max_grad_norm) in front of every step.  Over ONE tensor -- the flat training
+    loop -- that is two small launches for the norm and the coefficient (trajsde_grad_norm_clip: float64 sum of squares in a fixed
+    order) and the scaling inside the AdamW launch (trajsde_adamw_step_clipped, which leaves the scaled gradient in `.grad` as torch
+    would); over several tensors, or where the launch does not apply, torch's own clip_grad_norm_ runs first.  Either way the
+    [norm, coefficient] pair of the last step stays on the device as `last_grad_norm` (None before the first step and without a clip
+    value).  The clip value is configuration, not state: it is in neither state_dict() nor param_groups."""
 
-    def __init__(self, params, *args, form: str = "foreach", **kwargs) -> None:
+    def __init__(self, params, *args, form: str = "foreach", max_grad_norm: Optional[float] = None, **kwargs) -> None:
         if form not in ("foreach", "single"):
             raise ValueError(f"FlatAdamW form {form!r}: 'foreach' or 'single'")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"FlatAdamW max_grad_norm {max_grad_norm!r}: a positive number or None")
         self.form = form
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
+        self._clip_ws = None
         # what torch runs where the launch does not apply, and what a checkpoint's param_groups say: the multi-tensor form is torch's
         # own choice on a GPU when `foreach` is None (the reference's `AdamW(model.parameters())` stores None), the other is False
         kwargs.setdefault("foreach", None if form == "foreach" else False)
@@ -393,14 +424,40 @@ class FlatAdamW(torch.optim.AdamW):
 
     @torch.no_grad()
     def step(self, closure=None):
+        clip = self.max_grad_norm
         if not all(self._fast(g) for g in self.param_groups):
-            return super().step(closure)
+            if clip is None:
+                return super().step(closure)
+            loss = None
+            if closure is not None:                                          # the gradients are clipped after the closure formed them
+                with torch.enable_grad():
+                    loss = closure()
+            self.last_grad_norm = torch_clip_grad_norm([p for g in self.param_groups for p in g["params"]], clip)
+            super().step()
+            return loss
         from trajsde_amd import _lib
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         L = _lib.lib()
+        coef = None
+        if clip is not None:
+            with_grad = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+            if len(with_grad) == 1:                                          # one tensor: its norm is the global norm
+                p = with_grad[0]
+                n = p.numel()
+                need = int(L.trajsde_grad_norm_ws_bytes(n)) if n > 0 else -1
+                if need > 0:
+                    if self._clip_ws is None or self._clip_ws.device != p.device or self._clip_ws.numel() * 8 < need:
+                        self._clip_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=p.device)
+                    coef = torch.empty(2, dtype=torch.float32, device=p.device)    # a tensor per step: the loop reads it one step late
+                    with torch.cuda.device(p.device):
+                        _lib.check(L.trajsde_grad_norm_clip(p.grad.data_ptr(), n, clip, self._clip_ws.data_ptr(), self._clip_ws.numel() * 8,
+                                                            coef.data_ptr(), torch.cuda.current_stream().cuda_stream), "trajsde_grad_norm_clip")
+                    self.last_grad_norm = coef
+            if coef is None and with_grad:                                   # several tensors: torch's norm of norms and in-place scaling
+                self.last_grad_norm = torch_clip_grad_norm(with_grad, clip)
         for group in self.param_groups:
             lr, (beta1, beta2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             for p in group["params"]:
@@ -416,6 +473,13 @@ class FlatAdamW(torch.optim.AdamW):
                 bias1, bias2 = 1 - beta1 ** step, 1 - beta2 ** step
                 with torch.cuda.device(p.device):
                     divide = self.form == "foreach"
+                    if coef is not None:
+                        _lib.check(L.trajsde_adamw_step_clipped(p.data_ptr(), p.grad.data_ptr(), state["exp_avg"].data_ptr(),
+                                                                state["exp_avg_sq"].data_ptr(), p.numel(), 1 - lr * wd, 1 - beta1, beta2, 1 - beta2,
+                                                                bias2 ** 0.5 if divide else 1.0 / (bias2 ** 0.5), int(divide), eps, -(lr / bias1),
+                                                                coef.data_ptr() + 4, torch.cuda.current_stream().cuda_stream),
+                                   "trajsde_adamw_step_clipped")
+                        continue
                     _lib.check(L.trajsde_adamw_step(p.data_ptr(), p.grad.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
                                                     p.numel(), 1 - lr * wd, 1 - beta1, beta2, 1 - beta2,
                                                     bias2 ** 0.5 if divide else 1.0 / (bias2 ** 0.5), int(divide), eps, -(lr / bias1),
@@ -431,9 +495,14 @@ class FlatTraining:
     GPU side of a training step is down to ~13 ms.  Parameters the losses do not reach keep `.grad = None` and are not in the
     optimizer, exactly what torch's AdamW does with them (it skips parameters without a gradient, weight decay included).
     The optimizer state holds one tensor; checkpoints store it cut back into the per-parameter layout of the reference's
-    `AdamW(self.parameters())` (optimizer_state_dict / load_optimizer_state_dict), so either side resumes the other's."""
+    `AdamW(self.parameters())` (optimizer_state_dict / load_optimizer_state_dict), so either side resumes the other's.
+    `model.gradient_clip_val` (Lightning's name; None or 0: off) clips the global gradient norm in `step()` -- under several ranks
+    after `all_reduce_mean()`, so every rank scales the same averaged buffer by the same coefficient and no collective is added.
+    `last_grad_norm`: the step's [norm before clipping, coefficient] on the device, None while clipping is off."""
 
     def __init__(self, model) -> None:
+        self.max_grad_norm = clip_value_of(model)
+        self._torch_norm = None
         params = [p for p in model.params_with_gradient() if p.requires_grad]
         ref = params[0]
         flat = torch.cat([p.detach().reshape(-1) for p in params]).to(ref.dtype).contiguous()
@@ -463,7 +532,7 @@ class FlatTraining:
                                                foreach=bool(getattr(model, "adamw_foreach", False)))
         else:
             self.optimizer = FlatAdamW([self.flat_param], lr=model.lr, weight_decay=model.weight_decay,
-                                       form=str(getattr(model, "adamw_form", "foreach")))
+                                       form=str(getattr(model, "adamw_form", "foreach")), max_grad_norm=self.max_grad_norm)
         if hasattr(model, "scheduler_step"):
             self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=model.scheduler_step, gamma=model.scheduler_gamma)
         else:
@@ -476,7 +545,13 @@ class FlatTraining:
     def all_reduce_mean(self) -> None:
         self.grads.all_reduce_mean()
 
+    @property
+    def last_grad_norm(self):
+        return self.optimizer.last_grad_norm if isinstance(self.optimizer, FlatAdamW) else self._torch_norm
+
     def step(self) -> None:
+        if self.max_grad_norm is not None and not isinstance(self.optimizer, FlatAdamW):      # torch's own AdamW: torch's own clip
+            self._torch_norm = torch_clip_grad_norm([self.flat_param], self.max_grad_norm)
         self.optimizer.step()
         for m in self._stages:                               # the slices' version counters did not move: tell the weight packers
             m.touch()
@@ -551,9 +626,12 @@ class FlatTraining:
 
 class PlainTraining:
     """the same handle over the model's own `configure_optimizers()` (per-parameter optimizer, flat gradient bucket): for
-    modules that define their optimizer themselves and not the (lr, weight_decay, T_max) recipe FlatTraining rebuilds"""
+    modules that define their optimizer themselves and not the (lr, weight_decay, T_max) recipe FlatTraining rebuilds.
+    `model.gradient_clip_val`: torch.nn.utils.clip_grad_norm_ over the optimizer's parameters before its step."""
 
     def __init__(self, model) -> None:
+        self.max_grad_norm = clip_value_of(model)
+        self.last_grad_norm = None
         (self.optimizer,), (self.scheduler,) = model.configure_optimizers()
         model.optimizer, model.scheduler = self.optimizer, self.scheduler
         self.grads = FlatGrads(model.params_with_gradient())
@@ -567,6 +645,8 @@ class PlainTraining:
         self.grads.all_reduce_mean()
 
     def step(self) -> None:
+        if self.max_grad_norm is not None:
+            self.last_grad_norm = torch_clip_grad_norm([p for g in self.optimizer.param_groups for p in g["params"]], self.max_grad_norm)
         self.optimizer.step()
 
     def optimizer_state_dict(self) -> dict:
@@ -615,7 +695,8 @@ def train(model, batches_per_epoch, epochs: int, seed: int = 0, log=None, ckpt_p
           resume: Optional[str] = None) -> list:
     """trainer.fit(...) spelled out (train.py:60-66): per batch zero -> training_step -> backward -> gradient
     all-reduce -> AdamW step; scheduler step per epoch.  `batches_per_epoch(epoch)` yields this rank's batches.
-    `ckpt_path`: rank 0 writes a checkpoint after every epoch; `resume`: continue from such a file (weights, AdamW
+    `model.gradient_clip_val` clips the global gradient norm in the step (FlatTraining / PlainTraining) and `log` then gets the norm
+    before clipping as `parts["grad_norm"]`.  `ckpt_path`: rank 0 writes a checkpoint after every epoch; `resume`: continue from such a file (weights, AdamW
     moments, schedule, epoch and step counters -- the noise seeds continue where they stopped, so a resumed run
     retraces the uninterrupted one).  Returns the per-step loss values of this rank."""
     model.train()
@@ -644,9 +725,15 @@ def train(model, batches_per_epoch, epochs: int, seed: int = 0, log=None, ckpt_p
                     if opt.form == "foreach" else "one launch over the flat tensor, the bits of torch's single-tensor AdamW (foreach=False)")
         else:
             form = "torch's multi-tensor AdamW (foreach)" if getattr(model, "adamw_foreach", False) else "torch's / the model's own optimizer"
+        if flat.max_grad_norm is None:
+            clip = "off"
+        elif isinstance(opt, FlatAdamW):
+            clip = f"global norm {flat.max_grad_norm:g}, two launches for the norm and the scaling inside the AdamW launch"
+        else:
+            clip = f"global norm {flat.max_grad_norm:g}, torch.nn.utils.clip_grad_norm_"
         print(f"[trajsde_amd.driver] AdamW form: {form}; gradient all-reduce: "
-              f"{'two slices, decoder+aggregator early' if flat.grads.early_enabled else ('one piece' if dist_on else 'none (one rank)')}",
-              file=sys.stderr)
+              f"{'two slices, decoder+aggregator early' if flat.grads.early_enabled else ('one piece' if dist_on else 'none (one rank)')}"
+              f"; gradient clipping: {clip}", file=sys.stderr)
     rank = torch.distributed.get_rank() if dist_on else 0
     rank0 = rank == 0
     history = []
@@ -672,8 +759,10 @@ def train(model, batches_per_epoch, epochs: int, seed: int = 0, log=None, ckpt_p
 
     def settle(pending):
         if pending is not None:
-            loss_t, epoch_, i_, parts = pending
+            loss_t, epoch_, i_, parts, norm_t = pending
             history.append(float(loss_t))
+            if norm_t is not None:                            # the step's gradient norm before clipping: on the device until here, where
+                parts["grad_norm"] = float(norm_t[0])         # the loss has just been waited for
             if log:
                 log(epoch_, i_, history[-1], parts)
 
@@ -689,7 +778,7 @@ def train(model, batches_per_epoch, epochs: int, seed: int = 0, log=None, ckpt_p
             loss.backward()
             flat.all_reduce_mean()
             flat.step()
-            mine = (loss.detach(), epoch, i, dict(getattr(model, "last_losses", None) or {}))
+            mine = (loss.detach(), epoch, i, dict(getattr(model, "last_losses", None) or {}), flat.last_grad_norm)
             step += 1
             batch = fetch(it, step)
             settle(pending)
@@ -759,7 +848,7 @@ def datamodule_train_batches(cfg: dict, device, rank: int = 0, world: int = 1, n
     return per_epoch
 
 
-def main() -> None:
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("-c", "--config", required=True)
     ap.add_argument("--ckpt", default=None)
@@ -774,7 +863,14 @@ def main() -> None:
     ap.add_argument("--nu_dir", default=None)
     ap.add_argument("--argo_dir", default=None)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    ap.add_argument("--gradient-clip-val", "--gradient_clip_val", dest="gradient_clip_val", type=float, default=None, metavar="FLOAT",
+                    help="--train: clip the global gradient norm to FLOAT before every optimizer step (Lightning's "
+                         "Trainer(gradient_clip_val=...); 0 or absent: no clipping)")
+    return ap
+
+
+def main() -> None:
+    args = arg_parser().parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -801,13 +897,16 @@ def main() -> None:
     dev = torch.device("cuda", local_rank)
     model = build_model(cfg, args.ckpt, dev, init_seed=0 if args.ckpt is None else None)
     if args.train:
+        model.gradient_clip_val = args.gradient_clip_val
         if args.data:
             per_epoch = datamodule_train_batches(cfg, dev, rank, world, args.nu_dir, args.argo_dir)
         else:
             def per_epoch(epoch):
                 return synthetic_batches(args.synthetic, args.batches, dev, rank, world, even=True)
         hist = train(model, per_epoch, args.epochs, ckpt_path=args.save, resume=args.resume,
-                     log=(lambda e, i, l, parts: print(f"epoch {e} step {i} loss {l:.5f}")) if rank == 0 else None)
+                     log=(lambda e, i, l, parts: print(f"epoch {e} step {i} loss {l:.5f}"
+                                                      + (f" grad_norm {parts['grad_norm']:.5f}" if "grad_norm" in parts else "")))
+                     if rank == 0 else None)
         if rank == 0:
             print(json.dumps({"steps": len(hist), "first_loss": hist[0], "last_loss": hist[-1]}))
         if world > 1:
