@@ -39,11 +39,11 @@ def _rotated(batch, dev):
 
 
 # ------------------------------------------------------------------ 1. vjp parity, stage level
-def _stage_case(N, K, T, dev):
+def _stage_case(N, K, T, dev, max_t=None):
     """seeded random embeddings, cotangents and injected normals for a decoder at trained-like weights"""
     from trajsde_amd.schedule import decoder_schedule
     from trajsde_amd.synth import synth
-    max_t = T / 10.0
+    max_t = T / 10.0 if max_t is None else max_t
     model, cfg = H.build_model(K, T, max_t, init_seed=21)
     H.trained_like_parameters(model, H.TRAINED_SEED, 1.0)
     model = model.to(dev)
@@ -189,6 +189,43 @@ def test_zero_cotangents_repeat_and_noise_sources(dev):
     _check_range()
     bad = H.compare_grads("cotangent seed vs injected z", c, a, rel=2e-5)
     assert not bad, bad
+
+
+# ------------------------------------------------------------------ 3b. both forms of the replay and the sweep
+FORMS_SEED = 77
+
+
+def _forms_case(dev):
+    """K * N = 3 * 17 = 51 paths (three full 16-row tiles and a ragged one; 17 actors: a full tile and a ragged one), T = 5 output steps over
+    n_euler = 6 Euler steps (max_fut_t 0.6 at step 0.1): the smallest case with a partial tile, more than one mode and n_euler != T"""
+    case = _stage_case(17, 3, 5, dev, max_t=0.6)
+    assert case[3].n_euler == 6
+    return case
+
+
+def test_both_kernel_forms_match_float64_autograd(dev, tmp_path):
+    """The cotangent route reaches the replay and the sweep through the host helpers it shares with the welded entry points
+    (csrc/decoder_bwd_host.hpp), on the row domain (K * N, 1).  Once with the default switches (the cooperative kernels in the fp16x3
+    build) and once with TRAJSDE_REPLAY_COOP=0 TRAJSDE_SWEEP_COOP=0 (the one-wave kernels), each in a fresh process since the switches
+    are read once; seeded noise; every gradient against float64 autograd over the oracle under the file's rule."""
+    import os
+    import subprocess
+    import sys
+
+    import restate
+    model, cfg, batch, sched, t = _forms_case(torch.device("cpu"))
+    want = _oracle_vjp(model, cfg, batch, sched, t, restate.PhiloxNoise(FORMS_SEED))
+    for tag, switches in (("default", {}), ("one-wave", {"TRAJSDE_REPLAY_COOP": "0", "TRAJSDE_SWEEP_COOP": "0"})):
+        env = {k: v for k, v in os.environ.items() if k not in ("TRAJSDE_REPLAY_COOP", "TRAJSDE_SWEEP_COOP")}
+        env.update(switches)
+        out = str(tmp_path / (tag + ".pt"))
+        r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "cotangent_forms_child.py"), out], env=env, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, (tag, r.stdout[-2000:], r.stderr[-2000:])
+        got = torch.load(out)
+        assert set(got) <= set(want) and all(float(got[k].abs().max()) > 0.0 for k in PI + SCALE), tag
+        bad = H.compare_grads(f"cotangent forms {tag}", got, want)
+        assert not bad, (tag, bad)
 
 
 # ------------------------------------------------------------------ 4. end to end

@@ -513,3 +513,27 @@ def test_ranks_of_a_node_get_disjoint_core_shares_and_capped_thread_pools():
     one = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, LOCAL_RANK="0", LOCAL_WORLD_SIZE="1", WORLD_SIZE="1"),
                          capture_output=True, text=True, timeout=120)
     assert json.loads(one.stdout.strip().splitlines()[-1])[0]["pinned"] is False          # single-rank runs are left alone
+
+
+# (N, K, T, n_euler) -> bytes of the L2, NLL, Milstein and cotangent decoder backward queries, then of the MLP decoder's cotangent query
+# (N, K, T).  Literals: returned by the library built from the commit before the weight-gradient engine moved to csrc/wgrad.hip and the
+# cotangent entry point to csrc/decoder_cot_bwd.hip; that change was to leave every workspace layout as it was.  Cross-checks in
+# 3 669 096 448 B = 3.42 GiB (cotangent, 64 x 128 agents, K = 6, T = 20) and 231 867 648 B (MLP route, T = 30).
+WS_BYTES = {
+    (1, 1, 5, 5): (42086912, 42088192, 42126080, 42089216, 37353216),
+    (17, 6, 5, 6): (42429952, 42451712, 42588928, 44334080, 37749248),
+    (33, 6, 20, 20): (44568320, 44737280, 45445888, 56916480, 38126080),
+    (8192, 6, 20, 20): (602027776, 643970816, 811775744, 3669096448, 231867648),
+}
+
+
+def test_decoder_backward_workspace_queries_are_pinned():
+    from trajsde_amd import _lib
+    L = _lib.lib()
+    sde = [L.trajsde_decoder_backward_ws_bytes, L.trajsde_decoder_nll_backward_ws_bytes, L.trajsde_decoder_milstein_backward_ws_bytes,
+           L.trajsde_decoder_cotangent_backward_ws_bytes]
+    for shape, want in WS_BYTES.items():
+        got = [q(*shape) for q in sde] + [L.trajsde_mlp_decoder_cotangent_backward_ws_bytes(*shape[:3])]
+        assert tuple(got) == want, (shape, got, want)
+    assert L.trajsde_mlp_decoder_cotangent_backward_ws_bytes(8192, 6, 30) == 231867648
+    assert round(WS_BYTES[(8192, 6, 20, 20)][3] / 2 ** 30, 2) == 3.42

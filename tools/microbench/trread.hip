@@ -1,4 +1,4 @@
-// Lane map of ds_read_b64_tr_b16 (gfx950) as csrc/decoder_bwd.hip k_wgrad6 uses it: a [rows][64 halves] LDS image, group g of 16 lanes
+// Lane map of ds_read_b64_tr_b16 (gfx950) as csrc/wgrad.hip k_wgrad6 uses it: a [rows][64 halves] LDS image, group g of 16 lanes
 // reads rows 8g .. 8g+3; lane 4q+p of the group supplies the address of row q, columns 4p .. 4p+3.  Expected (cdna_hip_programming.md T10):
 // lane i of the group receives column i of the four rows.   hipcc --offload-arch=gfx950 -O3 -o trread trread.hip && ./trread
 #include <hip/hip_runtime.h>

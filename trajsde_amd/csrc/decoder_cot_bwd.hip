@@ -1,4 +1,4 @@
-// decoder_cot_bwd.hip -- kernels of trajsde_decoder_cotangent_backward (host side: decoder_bwd.hip), the SDEDecoder's backward from
+// decoder_cot_bwd.hip -- trajsde_decoder_cotangent_backward (kernels, then the entry point at the end), the SDEDecoder's backward from
 // caller-supplied cotangents dL/dloc [K,N,T,4] and dL/dpi [N,K] for gfx950.  Every one of the K * N paths carries gradient, so the
 // replay and the reverse sweep of decoder_bwd.hip / recur.hip run over a row domain of K * N with the identity selection (row
 // r = k * N + n is path r: the forward's Philox counter); what is new here is what the welded entry points fuse with their loss or
@@ -12,12 +12,14 @@
 //                        input gradients to d_local / d_global
 //
 // The mode sums into d_local run inside ONE wave per 16 actors, modes 0..K-1 in order: no atomics, identical calls give identical words.
-// A separate unit so that the kernels of decoder_bwd.hip keep their listings.
+// A separate unit so that the kernels of decoder_bwd.hip keep their listings.  The host side shares the replay, the sweep and the SDE
+// weight gradients with the welded entry points (decoder_bwd_host.hpp, defined in decoder_bwd.hip).
 #include "common.hpp"
 #include "layouts.hpp"
 #include "tile.hpp"
 #include "tile_bwd.hpp"
 #include "bwd.hpp"
+#include "decoder_bwd_host.hpp"
 
 namespace tsde {
 
@@ -290,4 +292,140 @@ __global__ __launch_bounds__(128) void k_pi_head_bwd(const float* __restrict__ i
   flush_scalar(db3, vp + PiV::DB3, L);
 }
 
+// ------------------------------------------------------------------ host side
+// trajsde_decoder_cotangent_backward: the Laplace NLL workspace over a row domain of K * N (every path is replayed and swept), then the
+// pi head's delta rows and the two mode sums of delta rows whose input row is the actor's local embedding
+struct CotWs {
+  BwdWs w;
+  float *DP, *DAS, *DPS;
+  int64_t bytes;
+};
+static CotWs carve_cot(void* ws, int64_t ws_bytes, int N, int K, int T, int n_euler, bool& ok) {
+  CotWs c;
+  const int NN = N * K;
+  c.w = carve_bwd(ws, ws_bytes, NN, T, n_euler, ok, true);
+  Carver cv(ws ? reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(ws) + uintptr_t(c.w.bytes)) : nullptr, ws_bytes - c.w.bytes);
+  c.DP = cv.take<float>(int64_t(NN) * 64);
+  c.DAS = cv.take<float>(int64_t(N) * 64);
+  c.DPS = cv.take<float>(int64_t(N) * 64);
+  c.bytes = c.w.bytes + cv.off + 256;
+  ok = ok && cv.ok;
+  return c;
+}
+
+// the largest K * N * max(T, n_euler) the row indices of the kernels hold (tiles and rows are 32-bit there, offsets 64-bit)
+static bool cot_rows_ok(int32_t N, int K, int T, int n_euler) {
+  return N > 0 && K > 0 && T > 0 && n_euler > 0 && int64_t(N) * K * (T > n_euler ? T : n_euler) < (int64_t(1) << 31) - 64;
+}
+
 }  // namespace tsde
+
+using namespace tsde;
+
+extern "C" {
+
+int64_t trajsde_decoder_cotangent_backward_ws_bytes(int32_t N, int num_modes, int future_steps, int n_euler) {
+  if (!cot_rows_ok(N, num_modes, future_steps, n_euler)) return fail(TRAJSDE_ERR_INVALID, "decoder_cotangent_backward: empty or oversized problem");
+  bool ok;
+  return carve_cot(nullptr, 0, N, num_modes, future_steps, n_euler, ok).bytes;
+}
+
+int trajsde_decoder_cotangent_backward(int32_t N, int num_modes, int future_steps, const float* blob_fwd, const float* blob_bwd,
+                                       const float* local_embed, const float* global_embed, const float* step_table, int n_euler,
+                                       const float* out_table, const trajsde_noise* noise, const float* loc, float min_scale,
+                                       const float* d_loc, const float* d_pi, void* ws, int64_t ws_bytes, float* const* grads, int n_grads,
+                                       float* d_local, float* d_global, void* stream_) {
+  TS_REQUIRE(blob_fwd && blob_bwd && local_embed && global_embed && step_table && out_table && loc && d_loc && d_pi && ws && grads &&
+                 d_local && d_global,
+             "decoder_cotangent_backward: null pointer");
+  TS_REQUIRE(cot_rows_ok(N, num_modes, future_steps, n_euler), "decoder_cotangent_backward: empty or oversized problem");
+  TS_REQUIRE(n_grads == int(N_GRADS_COT),
+             "decoder_cotangent_backward: gradient count does not match trajsde_param_count(TRAJSDE_STAGE_DECODER_COT_BWD)");
+  for (int i = 0; i < int(N_GRADS_COT); ++i) TS_REQUIRE(grads[i] != nullptr, "decoder_cotangent_backward: null gradient buffer");
+  if (state_bf16())
+    return fail(TRAJSDE_ERR_UNSUPPORTED, "decoder_cotangent_backward: trajsde_state_storage(1) is not supported (the replay keeps fp32 states)");
+  if (ws_bytes < trajsde_decoder_cotangent_backward_ws_bytes(N, num_modes, future_steps, n_euler))
+    return fail(TRAJSDE_ERR_WORKSPACE, "decoder_cotangent_backward: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  bool ok;
+  const int K = num_modes, T = future_steps, NN = N * K;
+  const CotWs cw = carve_cot(ws, ws_bytes, N, K, T, n_euler, ok);
+  const BwdWs& w = cw.w;
+  DeferredSums sums(st, w.part, w.cs, w.parts, step_table, w.varena, w.varena_floats);
+  const NoiseArg na = noise_arg(noise);
+  const int ntiles = (NN + 15) / 16, atiles = (N + 15) / 16;
+  const int waves = BWD_THREADS / 64;
+  int rc;
+
+  // ---- replay of every path: the replay and sweep kernels select path best[i] * N' + i of N' * K' -- the identity over N' = K * N, K' = 1
+  TS_HIP(hipMemsetAsync(w.best, 0, sizeof(int32_t) * NN, st));
+  const float* init_img = blob_bwd + DecBwdBlob::INIT;
+  TS_LAUNCH(k_init_all, bwd_grid(ntiles), BWD_THREADS, InitBwdL::AE_END * 4, st, init_img, local_embed, global_embed, N, K, w.states);
+  if ((rc = launch_replay(st, blob_fwd, w, NN, 1, n_euler, step_table, na, false))) return rc;
+
+  // ---- both heads from the cotangent, one pass over the saved states
+  int head_grid = bwd_grid(ntiles * T);
+  if (int64_t(head_grid) * waves * CotHeadV::SIZE > SHARED_VPART_FLOATS) head_grid = int(SHARED_VPART_FLOATS / (waves * CotHeadV::SIZE));
+  const int head_waves = head_grid * waves;
+  float* vp = vpart_slab(w.vpart, head_waves, CotHeadV::SIZE);
+  TS_LAUNCH(k_head_bwd_cot, head_grid, BWD_THREADS, 2 * HeadBwdL::SIZE * 4, st, blob_bwd + DecBwdBlob::HEAD, blob_bwd + DecNllBwdBlob::HEAD_SC,
+            w.states, out_table, loc, d_loc, min_scale, NN, T, w.S_in, w.DU, w.DU2, w.DS, vp);
+  {
+    ColsumBatch cb(st, head_waves, CotHeadV::SIZE);
+    head_colsums(cb, vp + CotHeadV::LOC, grads + D1W);
+    head_colsums(cb, vp + CotHeadV::SCALE, grads + S1W);
+    if ((rc = cb.flush())) return rc;
+  }
+
+  // ---- reverse sweep of every path
+  if ((rc = launch_sweep(st, blob_bwd, nullptr, w, NN, 1, T, n_euler, step_table, out_table, na, grads))) return rc;
+
+  // ---- aggr_embed over all modes (overwrites d_local, d_global), then the pi head (adds to both)
+  const int init_grid = bwd_grid(atiles);
+  vp = vpart_slab(w.vpart, int64_t(init_grid) * waves, InitV::SIZE);
+  TS_LAUNCH(k_dec_init_bwd_all, init_grid, BWD_THREADS, InitBwdL::SIZE * 4, st, init_img, local_embed, global_embed, w.DY0, N, K, w.DA, cw.DAS,
+            d_local, d_global, vp);
+  {
+    ColsumBatch cb(st, init_grid * waves, InitV::SIZE);
+    cb.add(vp + InitV::DGAM, 64, grads[A1W]);
+    cb.add(vp + InitV::DBET, 64, grads[A1B]);
+    if ((rc = cb.flush())) return rc;
+  }
+  vp = vpart_slab(w.vpart, int64_t(init_grid) * waves, PiV::SIZE);
+  TS_LAUNCH(k_pi_head_bwd, init_grid, BWD_THREADS, PiBwdL::SIZE * 4, st, blob_bwd + DecCotBwdBlob::PI, local_embed, global_embed, d_pi, N, K,
+            cw.DP, cw.DPS, d_local, d_global, vp);
+  {
+    ColsumBatch cb(st, init_grid * waves, PiV::SIZE);
+    cb.add(vp + PiV::DGAM, 64, grads[P1W]);
+    cb.add(vp + PiV::DBET, 64, grads[P1B]);
+    cb.add(vp + PiV::DW3, 64, grads[P3W]);
+    cb.add(vp + PiV::DB3, 1, grads[P3B]);
+    if ((rc = cb.flush())) return rc;
+  }
+
+  // ---- weight gradients
+  const WgradCtx wc{st, w.part, w.cs, step_table, w.parts};
+  const int64_t RT = int64_t(NN) * T;
+  if ((rc = sde_wgrads(wc, w, NN, n_euler, grads, false))) return rc;
+  {
+    WgradBatch heads(wc, RT, RT);                           // the two heads' first layers over the same (output step, path) rows
+    if ((rc = heads.add(w.DU, 64, w.S_in, 64, grads[D0W], 64, 0, grads[D0B], 0))) return rc;
+    if ((rc = heads.add(w.DU2, 64, w.S_in, 64, grads[S0W], 64, 0, grads[S0B], 0))) return rc;
+    if ((rc = heads.flush())) return rc;
+  }
+  {
+    WgradBatch glob(wc, NN, NN);                            // the global halves: aggr_embed.0 = cat(global, local), pi.0 = cat(local, global)
+    if ((rc = glob.add(w.DA, 64, global_embed, 64, grads[A0W], 128, 0, grads[A0B], 0))) return rc;
+    if ((rc = glob.add(cw.DP, 64, global_embed, 64, grads[P0W], 128, 64, grads[P0B], 0))) return rc;
+    if ((rc = glob.flush())) return rc;
+  }
+  {
+    WgradBatch loc_(wc, N, N);                              // the local halves: the mode-summed delta rows against the actors' rows
+    if ((rc = loc_.add(cw.DAS, 64, local_embed, 64, grads[A0W], 128, 64, nullptr, 0))) return rc;
+    if ((rc = loc_.add(cw.DPS, 64, local_embed, 64, grads[P0W], 128, 0, nullptr, 0))) return rc;
+    if ((rc = loc_.flush())) return rc;
+  }
+  return sums.finish();
+}
+
+}  // extern "C"

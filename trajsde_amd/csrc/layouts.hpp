@@ -425,7 +425,7 @@ struct DecBwdBlob {
 struct DecNllBwdBlob {   // Laplace NLL: the L2 blob followed by the scale head's images (forward + W0 transposed)
   enum : int { HEAD_SC = DecBwdBlob::SIZE, SIZE = HEAD_SC + HeadBwdL::SIZE };
 };
-// Backward from caller-supplied cotangents (decoder_bwd.hip trajsde_decoder_cotangent_backward): the Laplace NLL blob followed by the pi
+// Backward from caller-supplied cotangents (decoder_cot_bwd.hip trajsde_decoder_cotangent_backward): the Laplace NLL blob followed by the pi
 // head's images -- Linear(128,64) on cat(local, global) (DEC:93-94) as two forward halves and their transposes, LayerNorm, Linear(64,1)
 struct PiBwdL {
   enum : int {
@@ -443,7 +443,7 @@ struct DecCotBwdBlob {
 static_assert(DecNllBwdBlob::HEAD_SC % 4 == 0 && DecCotBwdBlob::PI % 4 == 0 && PiBwdL::SIZE * 4 <= 160 * 1024 &&
                   2 * HeadBwdL::SIZE * 4 <= 160 * 1024,
               "cotangent backward images: aligned, fit LDS (the two heads side by side)");
-// Milstein reverse sweep (decoder_bwd.hip sde_bwd_body<true>): the tangent pass of GFunc along the adjoint u -- W0y u, W2 h1' -- runs
+// Milstein reverse sweep (decoder_mil_bwd.hip k_sde_bwd_mil): the tangent pass of GFunc along the adjoint u -- W0y u, W2 h1' -- runs
 // through linear_adj on GFunc's y-columns of net.0 and net.2 UNTRANSPOSED and unscaled (the orientation linear_adj reads as W, where
 // the SweepL `*T` fields give W^T).  The TRAJSDE_STAGE_DECODER_MILSTEIN_BWD / _NLL_BWD blobs are the Euler backward blobs with this
 // image appended; in LDS it sits right behind the sweep image.

@@ -10,7 +10,7 @@
 //
 // Matrix products: tile.hpp linear_acc on forward images (recomputation) and linear_adj on transposed images (adjoints:
 // row-scaled split precision in the fp16x3 build, exact fp32 in the bf16x6 build); parameter gradients
-// that are matrices come from the saved rows through run_wgrad (decoder_bwd.hip), vectors from per-wave accumulators.
+// that are matrices come from the saved rows through run_wgrad (wgrad.hip), vectors from per-wave accumulators.
 #include "bwd.hpp"
 #include "common.hpp"
 #include "dropout.hpp"

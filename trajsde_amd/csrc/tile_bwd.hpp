@@ -1,4 +1,4 @@
-// tile_bwd.hpp -- wave-level pieces shared by the backward kernels (decoder_bwd.hip, node_bwd.hip, aggregator_bwd.hip):
+// tile_bwd.hpp -- wave-level pieces shared by the backward kernels (decoder_bwd.hip, decoder_cot_bwd.hip, node_bwd.hip, aggregator_bwd.hip):
 // LayerNorm backward on a row tile, transposed-image products, per-wave flushing of vector-gradient accumulators.
 #pragma once
 #include "tile.hpp"
