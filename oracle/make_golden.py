@@ -21,7 +21,7 @@ import ref_loader as R                                        # noqa: E402
 from trajsde_amd import philox                                # noqa: E402
 from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet  # noqa: E402
 from trajsde_amd.schedule import decoder_schedule            # noqa: E402
-from trajsde_amd.synth import synth                          # noqa: E402
+from trajsde_amd.synth import irregular_masks, synth         # noqa: E402
 
 CASES = {
     # name: (synth kwargs, num_modes, future_steps, max_fut_t, init_seed, noise_seed)
@@ -31,7 +31,24 @@ CASES = {
     "shipped_k10_t60": (dict(S=2, n=8, L=6, F=60, box=90.0, seed=14, mixed_source=True, history_dropout=0.3), 10, 60, 6.0, 3, 104),
     # `uncertain: False` (DEC:56, DEC:100-101): the decoder without its scale head, loc [K, N, T, 2]
     "plain_k3_t12": (dict(S=2, n=9, L=5, F=12, box=80.0, seed=16, mixed_source=True, history_dropout=0.3), 3, 12, 1.2, 6, 106, False),
+    # `irregular`: the batch goes through synth.irregular_masks (gaps, several bos, rows unobserved at step 20 or never, ragged futures)
+    "irregular_k3_t12": (dict(S=3, n=13, L=5, F=12, box=80.0, seed=31, mixed_source=True, irregular=True), 3, 12, 1.2, 7, 107),
 }
+
+
+def make_batch(skw):
+    """synth(**skw); a case whose kwargs carry `irregular` is put through irregular_masks with the same seed"""
+    skw = dict(skw)
+    irregular = skw.pop("irregular", False)
+    batch = synth(**skw)
+    return irregular_masks(batch, skw["seed"], skw["F"]) if irregular else batch
+
+
+def fixture_path(folder, name):
+    """tests/<folder>/<name>.npz; the irregular-mask fixtures other than the forward one live in sub-folders of tests/golden"""
+    path = os.path.join(ROOT, "tests", *folder.split("/"), name + ".npz")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    return path
 
 
 def our_cfg(num_modes, future_steps, max_fut_t, uncertain=True):
@@ -59,13 +76,15 @@ def philox_noise(seed, A, Nt, KN, n_euler, H=21):
 
 OOD_CASES = {
     "ood_k3_t5": (dict(S=2, n=7, L=5, F=5, box=70.0, seed=15, mixed_source=True, history_dropout=0.4), 3, 5, 0.5, 4, 105),
+    "ood_irregular_k3_t5": (dict(S=3, n=13, L=5, F=5, box=80.0, seed=32, mixed_source=True, irregular=True), 3, 5, 0.5, 9, 108),
 }
+OOD_FOLDERS = {"ood_irregular_k3_t5": "golden/irregular_ood"}
 
 
 def make_ood(name):
     """MODEL:89-98 with ood=True: encoder.forward_ood (10 stochastic recurrences) -> stds."""
     skw, K, T, max_t, init_seed, noise_seed = OOD_CASES[name]
-    batch = synth(**skw)
+    batch = make_batch(skw)
     ours = PredictionModelSDENet(**our_cfg(K, T, max_t), init_seed=init_seed)
     sd = {k: v.detach().clone() for k, v in ours.state_dict().items()}
     ref = R.build_reference_model(R.load_reference_cfg(num_modes=K, future_steps=T, max_fut_t=max_t))
@@ -88,8 +107,7 @@ def make_ood(name):
     for k in ("loc", "pi", "reg_mask", "stds"):
         fx[f"out.{k}"] = out[k].numpy()
     fx["mid.global_embed"] = caps["global_embed"].numpy()
-    path = os.path.join(ROOT, "tests", "golden_ood", name + ".npz")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = fixture_path(OOD_FOLDERS.get(name, "golden_ood"), name)
     np.savez_compressed(path, **fx)
     print(f"{name}: N={N} K={K} T={T} -> {os.path.getsize(path) / 1024:.0f} KiB")
 
@@ -97,7 +115,7 @@ def make_ood(name):
 def make(name):
     skw, K, T, max_t, init_seed, noise_seed = CASES[name][:6]
     uncertain = CASES[name][6] if len(CASES[name]) > 6 else True
-    batch = synth(**skw)
+    batch = make_batch(skw)
     ours = PredictionModelSDENet(**our_cfg(K, T, max_t, uncertain), init_seed=init_seed)
     sd = {k: v.detach().clone() for k, v in ours.state_dict().items()}
     rcfg = R.load_reference_cfg(num_modes=K, future_steps=T, max_fut_t=max_t)

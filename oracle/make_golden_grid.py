@@ -20,7 +20,7 @@ sys.path[:0] = [ROOT, HERE]
 import ref_loader as R                                        # noqa: E402
 import restate_grid                                           # noqa: E402
 from trajsde_amd.models.model_base_mix import PredictionModel  # noqa: E402
-from trajsde_amd.synth import synth                          # noqa: E402
+from make_golden import fixture_path, make_batch             # noqa: E402
 
 REF_CFG = "configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml"
 CASES = {
@@ -30,7 +30,10 @@ CASES = {
     "grid_k6_t30_h8": (dict(S=2, n=11, L=4, F=30, box=110.0, seed=23, source=1, history_dropout=0.3), 6, 30, 8, 3, 2),
     # `uncertain: False` (dec_hivt_nusargo_grid.py:31, :58-59): no scale head, loc [K, N, T, 2]
     "grid_plain_k3_t12_h4": (dict(S=2, n=8, L=5, F=12, box=80.0, seed=24, mixed_source=True, history_dropout=0.3), 3, 12, 4, 2, 3, False),
+    # irregular masks (synth.irregular_masks): the temporal transformer's key-padding mask with gaps and fully padded rows
+    "grid_irregular_k3_t12_h4": (dict(S=3, n=13, L=5, F=12, box=80.0, seed=35, mixed_source=True, irregular=True), 3, 12, 4, 2, 4),
 }
+FOLDERS = {"grid_irregular_k3_t12_h4": "golden/irregular_grid"}
 
 
 def torch1_transformer_encoder_forward(self, src, mask=None, src_key_padding_mask=None, **_):
@@ -60,7 +63,7 @@ def state_checksum(sd):
 def make(name):
     skw, K, T, heads, layers, init_seed = CASES[name][:6]
     uncertain = CASES[name][6] if len(CASES[name]) > 6 else True
-    batch = synth(**skw)
+    batch = make_batch(skw)
     with open(os.path.join(ROOT, "trajsde_amd/configs/mi355x_trmenc_mlpdec.yml")) as f:
         ours_cfg = edit(yaml.safe_load(f), K, T, heads, layers, uncertain)
     ours = PredictionModel(**ours_cfg, init_seed=init_seed)
@@ -98,8 +101,7 @@ def make(name):
     fx["out.y_rot"] = data.y.numpy()
     for k in ("local_embed", "global_embed", "temporal_out"):
         fx[f"mid.{k}"] = caps[k].numpy()
-    path = os.path.join(ROOT, "tests", "golden_grid", name + ".npz")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = fixture_path(FOLDERS.get(name, "golden_grid"), name)
     np.savez_compressed(path, **fx)
     print(f"{name}: N={batch.num_nodes} K={K} T={T} heads={heads} -> {os.path.getsize(path) / 1024:.0f} KiB; restatement deviation {dev}")
 

@@ -23,10 +23,9 @@ ROOT = os.path.dirname(HERE)
 sys.path[:0] = [ROOT, HERE]
 
 import ref_loader as R                                        # noqa: E402
-from make_golden import our_cfg, philox_noise, state_checksum  # noqa: E402
+from make_golden import fixture_path, make_batch, our_cfg, philox_noise, state_checksum  # noqa: E402
 from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet  # noqa: E402
 from trajsde_amd.schedule import decoder_schedule            # noqa: E402
-from trajsde_amd.synth import synth                          # noqa: E402
 
 CASES = {
     # name: (synth kwargs, num_modes, future_steps, max_fut_t, init_seed, noise_seed, full)
@@ -38,8 +37,30 @@ CASES = {
                               10, 60, 6.0, 8, 204, False),
     # the reference's losses/laplace_nll_loss.py in place of losses/L2.py (its scale head is trained under it)
     "train_nll_k3_t5": (dict(S=3, n=9, L=5, F=5, box=70.0, seed=25, mixed_source=True, history_dropout=0.3), 3, 5, 0.5, 10, 205, True),
+    # irregular masks (synth.irregular_masks): gaps, several bos, rows unobserved at step 20 or never, ragged and empty futures
+    "train_irregular_k3_t12": (dict(S=3, n=13, L=5, F=12, box=80.0, seed=33, mixed_source=True, irregular=True), 3, 12, 1.2, 11, 206, True),
 }
 NLL_CASES = {"train_nll_k3_t5"}
+FOLDERS = {"train_irregular_k3_t12": "golden/irregular_train", "train_grid_irregular_k3_t12_h4": "golden/irregular_train"}
+SPLIT = {"train_irregular_k3_t12"}    # stored as a folder of part files (every gradient tensor in full does not fit one small file)
+PART_BYTES = 640 << 10
+
+
+def save_parts(folder, name, fx):
+    """tests/<folder>/<name>/partNN.npz: the entries of `fx` in order, a new part whenever the next array would take the part's
+    raw size past PART_BYTES; tests/helpers.py load_train_fixture reads such a folder back as one fixture"""
+    parts, size = [{}], 0
+    for k, v in fx.items():
+        n = np.asarray(v).nbytes
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    paths = [fixture_path(f"{folder}/{name}", f"part{i:02d}") for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
 
 
 def digest_signs(key, n):
@@ -51,7 +72,7 @@ def digest_signs(key, n):
 
 def make(name):
     skw, K, T, max_t, init_seed, noise_seed, full = CASES[name]
-    batch = synth(**skw)
+    batch = make_batch(skw)
     ours = PredictionModelSDENet(**our_cfg(K, T, max_t), init_seed=init_seed)
     g = torch.Generator().manual_seed(1000 + init_seed)
     with torch.no_grad():                                     # leave the initial point: zero biases hide bias-gradient bugs
@@ -131,11 +152,14 @@ def make(name):
         else:                                                 # digest: norm, a seeded +-1 projection, the leading entries
             fx[f"digest.{k}"] = np.array([float(gr.norm()), float((gr * digest_signs(k, gr.numel())).sum())] +
                                          gr[:30].tolist(), dtype=np.float64)
-    path = os.path.join(ROOT, "tests", "golden_train", name + ".npz")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    np.savez_compressed(path, **fx)
+    if name in SPLIT:
+        sizes = [os.path.getsize(p) for p in save_parts(FOLDERS[name], name, fx)]
+    else:
+        path = fixture_path(FOLDERS.get(name, "golden_train"), name)
+        np.savez_compressed(path, **fx)
+        sizes = [os.path.getsize(path)]
     print(f"{name}: N={N} K={K} T={T} losses={[(n, round(float(l), 6)) for n, l in zip(ref.loss_names, parts)]} "
-          f"grads={n_grad} -> {os.path.getsize(path) / 1024:.0f} KiB")
+          f"grads={n_grad} -> {' + '.join(f'{b / 1024:.0f}' for b in sizes)} KiB")
 
 
 GRID_KINK_MARGIN = 5e-6           # (of 16 seeds tried per case the nearest input was above 5e-6 for two or three)
@@ -144,6 +168,7 @@ GRID_CASES = {
     "train_grid_k3_t12_h4": (dict(S=3, n=9, L=6, F=12, box=70.0, seed=23, mixed_source=True, history_dropout=0.3), 3, 12, 4, 2, 43),
     # model.train() with the YAML's dropout 0.1: the reference's 36 dropout calls served from the Philox host twin's masks
     "train_grid_drop_k3_t12_h4": (dict(S=3, n=9, L=6, F=12, box=70.0, seed=26, mixed_source=True, history_dropout=0.3), 3, 12, 4, 2, 37, 7311),
+    "train_grid_irregular_k3_t12_h4": (dict(S=3, n=13, L=5, F=12, box=80.0, seed=34, mixed_source=True, irregular=True), 3, 12, 4, 2, 46),
 }
 
 
@@ -190,7 +215,7 @@ def make_grid(name):
     from trajsde_amd.models.model_base_mix import PredictionModel
     skw, K, T, heads, layers, init_seed = GRID_CASES[name][:6]
     dropout_seed = GRID_CASES[name][6] if len(GRID_CASES[name]) > 6 else None
-    batch = synth(**skw)
+    batch = make_batch(skw)
     with open(os.path.join(ROOT, "trajsde_amd/configs/mi355x_trmenc_mlpdec.yml")) as f:
         ours_cfg = G.edit(yaml.safe_load(f), K, T, heads, layers)
     ours = PredictionModel(**ours_cfg, init_seed=init_seed)
@@ -262,7 +287,7 @@ def make_grid(name):
         n_grad += 1
         fx[f"digest.{k}"] = np.array([float(gr.norm()), float((gr * digest_signs(k, gr.numel())).sum())] + gr[:30].tolist(),
                                      dtype=np.float64)
-    path = os.path.join(ROOT, "tests", "golden_train", name + ".npz")
+    path = fixture_path(FOLDERS.get(name, "golden_train"), name)
     np.savez_compressed(path, **fx)
     print(f"{name}: N={batch.num_nodes} K={K} T={T} losses={[(n, round(float(l), 6)) for n, l in zip(ref.loss_names, parts)]} "
           f"grads={n_grad} -> {os.path.getsize(path) / 1024:.0f} KiB")

@@ -10,6 +10,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(ROOT, "tests", "golden", "*.npz")))
 
 
+# the irregular-mask fixtures other than the forward one (trajsde_amd/synth.py irregular_masks): name -> folder under tests/
+FIXTURE_FOLDERS = {"ood_irregular_k3_t5": "golden/irregular_ood", "grid_irregular_k3_t12_h4": "golden/irregular_grid",
+                   "train_irregular_k3_t12": "golden/irregular_train", "train_grid_irregular_k3_t12_h4": "golden/irregular_train"}
+
+
+def fixture_arrays(name, folder):
+    """{key: array} of tests/<folder>/<name>.npz, or of every part file of the folder tests/<folder>/<name>/ (a fixture too large
+    for one file); `folder` None: FIXTURE_FOLDERS[name]"""
+    base = os.path.join(ROOT, "tests", *(FIXTURE_FOLDERS[name] if folder is None else folder).split("/"), name)
+    files = sorted(glob.glob(os.path.join(base, "*.npz"))) if os.path.isdir(base) else [base + ".npz"]
+    assert files, base
+    arrays = {}
+    for f in files:
+        z = np.load(f)
+        assert not set(z.files) & set(arrays), f
+        arrays.update({k: z[k] for k in z.files})
+    return arrays
+
+
 def our_cfg(num_modes, future_steps, max_fut_t, uncertain=True):
     with open(os.path.join(ROOT, "trajsde_amd/configs/mi355x_sde_encoder_decoder.yml")) as f:
         cfg = yaml.safe_load(f)
@@ -264,17 +283,34 @@ def fixture_dropout(meta):
     return restate.PhiloxDropout(int(meta["dropout_seed"]), float(meta["dropout_p"]))
 
 
-def load_train_fixture(name):
+def load_train_fixture(name, folder=None):
+    """tests/golden_train/<name>.npz, or the fixture (a file, or a folder of part files) of that name under tests/<folder>"""
     from trajsde_amd.data import TemporalData
-    z = np.load(os.path.join(ROOT, "tests", "golden_train", name + ".npz"))
-    batch = TemporalData(**{k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in.")})
+    z = fixture_arrays(name, FIXTURE_FOLDERS.get(name, "golden_train") if folder is None else folder)
+    batch = TemporalData(**{k[3:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("in.")})
     batch["num_nodes"] = batch["x"].shape[0]
-    meta = {k[5:]: z[k].item() for k in z.files if k.startswith("meta.")}
-    losses = {k[5:]: float(z[k]) for k in z.files if k.startswith("loss.")}
-    weights = {k[7:]: float(z[k]) for k in z.files if k.startswith("weight.")}
-    grads = {k[5:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("grad.")}
-    digests = {k[7:]: z[k] for k in z.files if k.startswith("digest.")}
+    meta = {k[5:]: v.item() for k, v in z.items() if k.startswith("meta.")}
+    losses = {k[5:]: float(v) for k, v in z.items() if k.startswith("loss.")}
+    weights = {k[7:]: float(v) for k, v in z.items() if k.startswith("weight.")}
+    grads = {k[5:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("grad.")}
+    digests = {k[7:]: v for k, v in z.items() if k.startswith("digest.")}
     return batch, meta, losses, weights, grads, digests
+
+
+def load_ood_fixture(name, folder=None):
+    """(batch, meta, out) of an out-of-distribution forward fixture (oracle/make_golden.py make_ood)"""
+    from trajsde_amd.data import TemporalData
+    z = fixture_arrays(name, FIXTURE_FOLDERS.get(name, "golden_ood") if folder is None else folder)
+    batch = TemporalData(**{k[3:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("in.")})
+    batch["num_nodes"] = batch["x"].shape[0]
+    meta = {k[5:]: v.item() for k, v in z.items() if k.startswith("meta.")}
+    out = {k[4:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("out.")}
+    return batch, meta, out
+
+
+def load_grid_arrays(name, folder=None):
+    """{key: array} of a vanilla-HiVT forward fixture (oracle/make_golden_grid.py)"""
+    return fixture_arrays(name, FIXTURE_FOLDERS.get(name, "golden_grid") if folder is None else folder)
 
 
 def digest_signs(key, n):
@@ -396,6 +432,24 @@ def _synth(**kw):
     return synth(**kw)
 
 
+def _irregular(**kw):
+    from trajsde_amd.synth import irregular
+    return irregular(**kw)
+
+
+def _irregular_tiles_batch(T):
+    """scenes of 33, 70 and 1 actors under irregular masks (synth.irregular_masks deals its five row kinds round-robin, period 5,
+    over the 104 rows): every kind boundary falls on every offset of a 16-row tile (the single-actor scene last, see _isolated_batch)"""
+    from trajsde_amd.data import collate
+    from trajsde_amd.synth import irregular_masks, synth
+    return irregular_masks(collate([synth(S=1, n=n, L=5, F=T, box=box, seed=50 + i, source=i % 2)
+                                    for i, (n, box) in enumerate(((33, 90.0), (70, 130.0), (1, 30.0)))]), 77, T)
+
+
+# the irregular-mask batches among TRAINED_CASES (gaps, several bos, rows unobserved at step 20 or never, ragged and empty futures)
+IRREGULAR_CASES = ("irregular_k6_t20", "irregular_tiles_k6_t20")
+
+
 # the batches the weights of trained_like_parameters are tested on: name -> (K, T, max_fut_t, batch maker)
 TRAINED_CASES = {
     "mixed_k6_t20": (6, 20, 2.0, lambda: _synth(S=3, n=20, L=8, F=20, box=90.0, seed=9, mixed_source=True)),
@@ -403,6 +457,9 @@ TRAINED_CASES = {
     "shipped_k10_t60": (10, 60, 6.0, lambda: _synth(S=2, n=18, L=8, F=60, box=100.0, seed=33, mixed_source=True)),
     "isolated_k6_t20": (6, 20, 2.0, lambda: _isolated_batch(20)),
     "cache_edges_k6_t20": (6, 20, 2.0, lambda: _cache_edge_batch(20)),
+    # N + A = 42: no multiple of 16
+    "irregular_k6_t20": (6, 20, 2.0, lambda: _irregular(S=3, n=13, L=6, F=20, box=80.0, seed=41, mixed_source=True)),
+    "irregular_tiles_k6_t20": (6, 20, 2.0, lambda: _irregular_tiles_batch(20)),
 }
 TRAINED_STRENGTHS = (1.0, 2.0)
 TRAINED_SEED = 11

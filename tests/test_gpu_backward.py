@@ -829,7 +829,8 @@ def test_backward_is_linear_in_the_upstream_gradient_over_many_binades(scale, de
 
 
 @pytest.mark.parametrize("name", sorted(os.path.basename(p)[:-4] for p in
-                                        __import__("glob").glob(os.path.join(H.ROOT, "tests", "golden_train", "train_[!g]*.npz"))))
+                                        __import__("glob").glob(os.path.join(H.ROOT, "tests", "golden_train", "train_[!g]*.npz")))
+                         + ["train_irregular_k3_t12"])                     # tests/golden/irregular_train: synth.irregular_masks rows
 def test_training_step_matches_the_reference_training_step(name, dev):
     """loss and every parameter gradient of the HIP training step against what the REFERENCE's own model IN TRAIN MODE (dropout
     0.1 at its 20 sites, masks injected), its loss modules and torch.autograd produced for the same weights, batch, injected

@@ -39,7 +39,7 @@ def _rotated(batch, dev):
 
 
 # ------------------------------------------------------------------ 1. vjp parity, stage level
-def _stage_case(N, K, T, dev, max_t=None):
+def _stage_case(N, K, T, dev, max_t=None, batch=None):
     """seeded random embeddings, cotangents and injected normals for a decoder at trained-like weights"""
     from trajsde_amd.schedule import decoder_schedule
     from trajsde_amd.synth import synth
@@ -47,7 +47,8 @@ def _stage_case(N, K, T, dev, max_t=None):
     model, cfg = H.build_model(K, T, max_t, init_seed=21)
     H.trained_like_parameters(model, H.TRAINED_SEED, 1.0)
     model = model.to(dev)
-    batch = synth(S=1, n=N, L=4, F=T, box=60.0, seed=40 + N)
+    if batch is None:
+        batch = synth(S=1, n=N, L=4, F=T, box=60.0, seed=40 + N)
     assert batch.num_nodes == N
     g = torch.Generator().manual_seed(100 + N)
     sched = decoder_schedule(T, max_t, 0.1)
@@ -100,6 +101,33 @@ def test_vjp_matches_float64_autograd(N, K, T, dev):
         assert float(got[k].abs().max()) > 0.0, k
     got.update(d_local_embed=res["d_local_embed"], d_global_embed=res["d_global_embed"])
     bad = H.compare_grads(f"cotangent vjp N={N} K={K} T={T}", got, want)
+    assert not bad, bad
+
+
+def test_vjp_under_irregular_masks(dev):
+    """the cotangent entry point on trajsde_amd/synth.py irregular_masks rows, with the cotangent of loc zero wherever reg_mask is
+    off, as any masked loss hands it over: ragged futures, whole rows of zero cotangent next to live ones in a tile"""
+    import restate
+    from trajsde_amd import runtime
+    from trajsde_amd.synth import irregular
+    N, K, T = 39, 6, 20
+    model, cfg, batch, sched, t = _stage_case(N, K, T, dev, batch=irregular(S=3, n=13, L=6, F=T, box=60.0, seed=68, mixed_source=True))
+    noise = runtime.NoiseSpec(z_dec=t["z"].to(dev))
+    data = batch.to(dev)
+    local, glob = t["local"].to(dev), t["glob"].to(dev)
+    rt = model.decoder._rt
+    with torch.no_grad():
+        out = rt.decoder_forward(data, local, glob, noise)
+    reg = out["reg_mask"].cpu()
+    assert torch.equal(reg, ~batch["padding_mask"][:, 21:]) and int((~reg.any(1)).sum()) >= 10
+    t["d_loc"] = t["d_loc"] * reg[None, :, :, None]
+    res = rt.decoder_cotangent_backward(data, local, glob, out, noise, t["d_loc"].to(dev), t["d_pi"].to(dev))
+    _check_range()
+    want = _oracle_vjp(model, cfg, batch, sched, t, restate.InjectedNoise(None, None, t["z"]))
+    got = dict(res["grads"])
+    got.update(d_local_embed=res["d_local_embed"], d_global_embed=res["d_global_embed"])
+    assert all(bool(torch.isfinite(g).all()) for g in got.values())
+    bad = H.compare_grads(f"cotangent vjp, irregular masks, N={N} K={K} T={T}", got, want)
     assert not bad, bad
 
 

@@ -14,6 +14,7 @@ import helpers as H
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 GRID = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(H.ROOT, "tests", "golden_grid", "*.npz")))
+GRID.append("grid_irregular_k3_t12_h4")                      # tests/golden/irregular_grid: synth.irregular_masks rows
 
 
 @pytest.fixture(scope="module")
@@ -42,11 +43,11 @@ def _cfg(K, T, heads, layers, dropout=0.0):
 def test_vanilla_forward_matches_reference_golden(name, dev):
     from trajsde_amd.data import TemporalData
     from trajsde_amd.models.model_base_mix import PredictionModel
-    z = np.load(os.path.join(H.ROOT, "tests", "golden_grid", name + ".npz"))
-    batch = TemporalData(**{k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in.")})
+    z = H.load_grid_arrays(name)
+    batch = TemporalData(**{k[3:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("in.")})
     K, T, heads, layers = (int(z["meta." + k]) for k in ("num_modes", "future_steps", "num_heads", "num_temporal_layers"))
     cfg = _cfg(K, T, heads, layers)
-    plain = "meta.uncertain" in z.files and int(z["meta.uncertain"]) == 0
+    plain = "meta.uncertain" in z and int(z["meta.uncertain"]) == 0
     if plain:                                                    # dec_hivt_nusargo_grid.py:31: the decoder without its scale head
         cfg["decoder"]["kwargs"]["uncertain"] = False
     model = PredictionModel(**cfg, init_seed=int(z["meta.init_seed"])).eval().to(dev)
@@ -391,7 +392,7 @@ def test_vanilla_training_step_matches_end_to_end_autograd_and_trains(dev):
     assert len(hist) == 12 and sum(hist[-3:]) < sum(hist[:3]), hist
 
 
-@pytest.mark.parametrize("name", ["train_grid_k3_t12_h4", "train_grid_drop_k3_t12_h4"])
+@pytest.mark.parametrize("name", ["train_grid_k3_t12_h4", "train_grid_drop_k3_t12_h4", "train_grid_irregular_k3_t12_h4"])
 def test_vanilla_training_step_matches_the_reference_training_step(name, dev):
     """loss and parameter-gradient digests of the HIP training step of the vanilla variant against the REFERENCE's own model
     (models/model_base_mix.py), L2 module and torch.autograd (tests/golden_train/train_grid_*.npz): one fixture with dropout off,

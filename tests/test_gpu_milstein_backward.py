@@ -44,11 +44,12 @@ def _milstein_model(cfg, init_seed, strength):
     return model
 
 
-def _stage_case(S, n, K, T, max_t, kw, strength, dev, seed=300, init_seed=11, noise_seed=91):
+def _stage_case(S, n, K, T, max_t, kw, strength, dev, seed=300, init_seed=11, noise_seed=91, batch=None):
     """test_milstein_grad_cpu._stage_case with `method: milstein`, run on the GPU: the kernels' own embeddings and forward"""
     from trajsde_amd import runtime
     from trajsde_amd.synth import synth
-    batch = synth(S=S, n=n, L=6, F=T, box=80.0, seed=seed + n, **kw)
+    if batch is None:
+        batch = synth(S=S, n=n, L=6, F=T, box=80.0, seed=seed + n, **kw)
     cfg = H.our_cfg(K, T, max_t)
     model = _milstein_model(cfg, init_seed, strength).to(dev)
     data = batch.to(dev)
@@ -94,6 +95,22 @@ def test_milstein_decoder_nll_backward(S, n, K, T, max_t, kw, strength, dev):
     got = _check(f"Milstein decoder NLL K={K} T={T} s={strength}", res, model, cfg, batch, local, glob, y_rot, 1e-6, 2e-5)
     for k in ("scale.0.weight", "scale.0.bias", "scale.1.weight", "scale.1.bias", "scale.3.weight", "scale.3.bias"):
         assert k in got and float(got[k].abs().max()) > 0.0, k
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("loss", ["l2", "nll"])
+def test_milstein_decoder_backward_under_irregular_masks(loss, strength, dev):
+    """the Milstein pair on trajsde_amd/synth.py irregular_masks rows: ragged futures, actors without any valid future step"""
+    from trajsde_amd.synth import irregular
+    K, T = 4, 20
+    batch = irregular(S=3, n=13, L=6, F=T, box=60.0, seed=67, mixed_source=True)
+    model, cfg, batch, data, y_rot, noise, local, glob, out = _stage_case(3, 13, K, T, 2.0, None, strength, dev, batch=batch)
+    rt = model.decoder._rt
+    res = rt.decoder_nll_backward(data, local, glob, out, noise, eps=1e-6) if loss == "nll" else rt.decoder_l2_backward(data, local, glob, out, noise)
+    _check_range()
+    got = _check(f"Milstein decoder {loss}, irregular masks, K={K} T={T} s={strength}", res, model, cfg, batch, local, glob, y_rot,
+                 1e-6 if loss == "nll" else None, 2e-5 if loss == "nll" else 1e-5)
+    assert all(bool(torch.isfinite(g).all()) for g in got.values())
 
 
 # ------------------------------------------------------------------ whole training step

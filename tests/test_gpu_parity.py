@@ -169,9 +169,18 @@ def test_scene_independence_and_sharding_invariance(dev):
 
 def test_forward_ood_matches_reference_golden(dev):
     """the OOD path (MODEL:89-98, ENC:204-370): 10 stochastic encoder passes -> per-actor std"""
+    _forward_ood_golden("ood_k3_t5", dev)
+
+
+def test_forward_ood_matches_reference_golden_under_irregular_masks(dev):
+    """... on the reference's own output for synth.irregular_masks rows (tests/golden/irregular_ood)"""
+    _forward_ood_golden("ood_irregular_k3_t5", dev)
+
+
+def _forward_ood_golden(name, dev):
     from test_oracle_golden import _load_ood
     from trajsde_amd.runtime import NoiseSpec
-    batch, meta, out = _load_ood()
+    batch, meta, out = _load_ood(name)
     model, cfg = H.build_model(meta)
     model = model.to(dev)
     model.ood = True
@@ -418,14 +427,20 @@ def _sorted_cols(*rows):
     (4, 20, 5, dict(history_dropout=0.7)),
     (1, 160, 8, dict(mixed_source=True)),                                # rows of 159 in-edges: three ballot blocks, > 64 survivors per segment
     (5, 70, 12, dict(history_dropout=0.3, nus_sparsity=True)),           # rows straddling ballot-block boundaries at every offset
+    (3, 33, 6, dict(mixed_source=True, irregular=True)),                 # synth.irregular_masks: gaps, rows padded at step 20 or always
 ])
 def test_compacted_edge_lists_equal_the_oracle_edge_sets_exactly(S, n, L, kw, dev):
     """index work is exact: the compacted agent-agent (t, src, dst), global (src, dst) and lane-actor (lane, actor) lists are
     the oracle's lists as multisets, the rows are in canonical order, and the segment pointers are the CSR of the targets"""
     from trajsde_amd.runtime import NoiseSpec
     from trajsde_amd.synth import synth
+    from trajsde_amd.synth import irregular_masks
     K, T = 2, 5
+    kw = dict(kw)
+    irregular = kw.pop("irregular", False)
     batch = synth(S=S, n=n, L=L, F=T, box=130.0, seed=300 + n, **kw)
+    if irregular:
+        batch = irregular_masks(batch, 300 + n, T)
     if n > 1:                                                            # duplicated and shuffled input edges too
         g = torch.Generator().manual_seed(n)
         ei = torch.cat([batch["edge_index"], batch["edge_index"][:, :5]], dim=1)
@@ -896,6 +911,7 @@ def test_errors_are_loud(dev):
     (3, 14, 6, dict(mixed_source=True, history_dropout=0.4)),
     (1, 1, 2, dict()),                                                   # no agent-agent edge at all
     (6, 90, 40, dict(nus_sparsity=True)),                                # E_aa > 65536: streams of more than one edge
+    (3, 13, 6, dict(mixed_source=True, irregular=True)),                 # synth.irregular_masks: empty global segments, rows without a bos
 ])
 def test_sync_free_forward_is_bitwise_the_exact_forward(S, n, L, kw, dev):
     """trajsde_graph_prepare_async leaves the list lengths on the device and hands the kernels bounds; the kernels derive the
@@ -904,8 +920,13 @@ def test_sync_free_forward_is_bitwise_the_exact_forward(S, n, L, kw, dev):
     from trajsde_amd import runtime
     from trajsde_amd.runtime import NoiseSpec
     from trajsde_amd.synth import synth
+    from trajsde_amd.synth import irregular_masks
     K, T = 3, 6
+    kw = dict(kw)
+    irregular = kw.pop("irregular", False)
     batch = synth(S=S, n=n, L=L, F=T, box=60.0, seed=5, **kw)
+    if irregular:
+        batch = irregular_masks(batch, 5, T)
     model, cfg = H.build_model(K, T, 0.5, init_seed=3)
     model = model.to(dev).eval()
     assert runtime.sync_free()                                           # the default
@@ -1044,3 +1065,58 @@ def test_relative_pose_prefetch_on_a_side_stream_is_bitwise_the_default_forward(
         torch.cuda.synchronize()
     finally:
         runtime._OVERLAP_REL = prev
+
+
+# ----------------------------------------------------------------------------- irregular observation masks (synth.irregular_masks)
+def test_graph_replay_under_irregular_masks_is_the_eager_forward(dev):
+    """runtime.GraphedForward on a batch with gaps, rows padded at step 20 and rows never observed: bit for bit the eager forward"""
+    from trajsde_amd import runtime
+    from trajsde_amd.runtime import NoiseSpec
+    from trajsde_amd.synth import irregular
+    K, T = 3, 6
+    batch = irregular(S=3, n=13, L=6, F=T, box=60.0, seed=36, mixed_source=True)
+    model, cfg = H.build_model(K, T, 0.5, init_seed=6)
+    model = model.to(dev).eval()
+    gf = runtime.GraphedForward(model, batch.to(dev))
+    keys = ("loc", "pi", "diff_in", "diff_out")
+    for seed in (5, 77):
+        got = {k: gf(seed=seed)[k].clone() for k in keys}
+        with torch.no_grad():
+            want = model(batch.to(dev), noise=NoiseSpec(seed=seed))
+        for k in keys:
+            assert torch.equal(got[k], want[k]), (seed, k)
+            assert bool(torch.isfinite(got[k]).all()), k
+
+
+def test_scene_run_alone_under_irregular_masks_gives_the_same_rows(dev):
+    """test_scene_independence_and_sharding_invariance on irregular masks: the second scene of a two-scene batch run alone with the
+    same global Philox row ids (same bound, 1e-5) -- its rows padded at step 20 and its never-observed rows included"""
+    from trajsde_amd.data import collate
+    from trajsde_amd.runtime import NoiseSpec
+    from trajsde_amd.synth import irregular_masks, synth
+    K, T = 3, 5
+    model, cfg = H.build_model(K, T, 0.5, init_seed=9)
+    model = model.to(dev)
+    a = synth(S=1, n=13, L=4, F=T, box=60.0, seed=37)
+    b = synth(S=1, n=22, L=6, F=T, box=60.0, seed=38, source=1)
+    both = irregular_masks(collate([a, b]), 39, T)
+    na, nb = a.num_nodes, b.num_nodes
+    for k in ("padding_mask", "bos_mask", "x"):
+        b[k] = both[k][na:].clone()
+    assert int(b["padding_mask"][:, 20].sum()) >= 4 and int((~b["bos_mask"].any(1)).sum()) >= 2
+
+    def ids(lo, hi):
+        return torch.arange(lo, hi, dtype=torch.int32, device=dev)
+
+    tot = na + nb
+    full = NoiseSpec(seed=77, fake_row_ids=ids(0, 2), enc_row_ids=torch.cat([ids(0, tot), ids(tot, tot + 2)]),
+                     dec_row_ids=torch.cat([ids(k * tot, (k + 1) * tot) for k in range(K)]))
+    part = NoiseSpec(seed=77, fake_row_ids=ids(1, 2), enc_row_ids=torch.cat([ids(na, tot), ids(tot + 1, tot + 2)]),
+                     dec_row_ids=torch.cat([ids(k * tot + na, (k + 1) * tot) for k in range(K)]))
+    with torch.no_grad():
+        o2 = model(both.to(dev), noise=full)
+        o1 = model(b.to(dev), noise=part)
+    assert bool(torch.isfinite(o2["loc"]).all()) and bool(torch.isfinite(o1["loc"]).all())
+    assert H.maxdiff(o2["loc"][:, na:].cpu(), o1["loc"].cpu()) <= 1e-5
+    assert H.maxdiff(o2["pi"][na:].cpu(), o1["pi"].cpu()) <= 1e-5
+    assert H.maxdiff(o2["diff_in"][1:].cpu(), o1["diff_in"].cpu()) <= 1e-5 and H.maxdiff(o2["diff_out"][1:].cpu(), o1["diff_out"].cpu()) <= 1e-5

@@ -51,10 +51,11 @@ def _rotated(batch, dev):
 
 
 # ------------------------------------------------------------------ SDE decoder
-def _decoder_case(S, n, K, T, max_t, kw, strength, dev, seed, init_seed, noise_seed):
+def _decoder_case(S, n, K, T, max_t, kw, strength, dev, seed, init_seed, noise_seed, batch=None):
     from trajsde_amd import runtime
     from trajsde_amd.synth import synth
-    batch = synth(S=S, n=n, L=6, F=T, box=80.0, seed=seed + n, **kw)
+    if batch is None:
+        batch = synth(S=S, n=n, L=6, F=T, box=80.0, seed=seed + n, **kw)
     model, cfg = H.build_model(K, T, max_t, init_seed=init_seed)
     model = _trained(model, strength).to(dev)
     data, y_rot = _rotated(batch, dev)
@@ -177,6 +178,12 @@ def test_aggregator_backward_at_trained_weights(S, n, K, heads, kw, strength, de
     from trajsde_amd.synth import synth
     T = 5
     batch = H._cache_edge_batch(T) if kw is None else synth(S=S, n=n, L=6, F=T, box=80.0, seed=400 + n, **kw)
+    _aggregator_backward_check(batch, K, heads, strength, dev)
+
+
+def _aggregator_backward_check(batch, K, heads, strength, dev, T=5):
+    from trajsde_amd import runtime
+    from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet
     cfg = H.our_cfg(K, T, 0.5)
     cfg["aggregator"]["kwargs"]["num_heads"] = heads
     model = _trained(PredictionModelSDENet(**cfg, init_seed=13).eval(), strength).to(dev)
@@ -194,6 +201,7 @@ def test_aggregator_backward_at_trained_weights(S, n, K, heads, kw, strength, de
     got["d_local_embed"], want["d_local_embed"] = res["d_local_embed"], d_local
     bad = H.compare_grads(f"aggregator N={batch.num_nodes} heads={heads} s={strength}", got, want, noise32=noise32)
     assert not bad, bad
+    return got
 
 
 # ------------------------------------------------------------------ SDE encoder
@@ -208,7 +216,11 @@ def test_encoder_backward_at_trained_weights(S, n, kw, diff_weight, strength, de
     may be widened only to 2 x the float32 oracle's own deviation from float64 (test_encoder_backward_matches_autograd)"""
     from trajsde_amd import runtime
     from trajsde_amd.synth import synth
-    batch = synth(S=S, n=n, L=6, F=5, box=60.0, seed=500 + n, **kw)
+    _encoder_backward_check(synth(S=S, n=n, L=6, F=5, box=60.0, seed=500 + n, **kw), diff_weight, strength, dev)
+
+
+def _encoder_backward_check(batch, diff_weight, strength, dev, tag="encoder"):
+    from trajsde_amd import runtime
     model, cfg = H.build_model(2, 5, 0.5, init_seed=17)
     model = _trained(model, strength).to(dev)
     data, _ = _rotated(batch, dev)
@@ -224,8 +236,9 @@ def test_encoder_backward_at_trained_weights(S, n, kw, diff_weight, strength, de
         assert float(want[k].abs().max()) == 0.0, k
     noise32 = H.deviation(want32, want)
     got["d_aa_out"], want["d_aa_out"] = res["d_aa_out"], d_aa
-    bad = H.compare_grads(f"encoder diff_weight={diff_weight} s={strength}", got, want, noise32=noise32)
+    bad = H.compare_grads(f"{tag} diff_weight={diff_weight} s={strength}", got, want, noise32=noise32)
     assert not bad, bad
+    return res, got
 
 
 # ------------------------------------------------------------------ vanilla variant: grid encoder, MLP decoder
@@ -237,7 +250,11 @@ def test_encoder_backward_at_trained_weights(S, n, kw, diff_weight, strength, de
 def test_vanilla_encoder_backward_at_trained_weights(S, n, heads, layers, kw, strength, dev):
     from trajsde_amd.models.model_base_mix import PredictionModel
     from trajsde_amd.synth import synth
-    batch = synth(S=S, n=n, L=6, F=5, box=60.0, seed=900 + n, **kw)
+    _vanilla_encoder_backward_check(synth(S=S, n=n, L=6, F=5, box=60.0, seed=900 + n, **kw), heads, layers, strength, dev)
+
+
+def _vanilla_encoder_backward_check(batch, heads, layers, strength, dev, tag="vanilla encoder"):
+    from trajsde_amd.models.model_base_mix import PredictionModel
     cfg = H.grid_cfg(2, 5, heads, layers)
     model = _trained(PredictionModel(**cfg, init_seed=5), strength).to(dev)
     data, _ = _rotated(batch, dev)
@@ -250,8 +267,9 @@ def test_vanilla_encoder_backward_at_trained_weights(S, n, heads, layers, kw, st
     want = {k[len("encoder."):]: w for k, w in want.items() if k.startswith("encoder.")}
     for k in set(want) - set(res["grads"]):
         assert want[k] is None or float(want[k].abs().max()) == 0.0, k
-    bad = H.compare_grads(f"vanilla encoder heads={heads} layers={layers} s={strength}", res["grads"], want)
+    bad = H.compare_grads(f"{tag} heads={heads} layers={layers} s={strength}", res["grads"], want)
     assert not bad, bad
+    return res["grads"]
 
 
 def _pad_future(batch, T, seed, empty_every=0):
@@ -275,6 +293,13 @@ def test_mlp_decoder_backward_at_trained_weights(loss, S, n, K, T, empty, streng
     from trajsde_amd.synth import synth
     seed = 800 + n + K
     batch = _pad_future(synth(S=S, n=n, L=5, F=T, box=80.0, seed=seed, mixed_source=True, history_dropout=0.3), T, seed, empty)
+    _mlp_decoder_backward_check(batch, loss, K, T, strength, dev)
+
+
+def _mlp_decoder_backward_check(batch, loss, K, T, strength, dev, tag="MLP decoder"):
+    import grid_nll_restate as G
+    import restate_grid
+    from trajsde_amd.models.model_base_mix import PredictionModel
     cfg = G.nll_cfg(K, T, 4, 2) if loss == "nll" else H.grid_cfg(K, T, 4, 2)
     model = _trained(PredictionModel(**cfg, init_seed=3), strength).to(dev)
     data = batch.to(dev)
@@ -306,8 +331,9 @@ def test_mlp_decoder_backward_at_trained_weights(loss, S, n, K, T, empty, streng
         assert all(float(got[k].abs().max()) > 0 for k in got if k.startswith("scale."))
     got.update(d_local_embed=res["d_local_embed"], d_global_embed=res["d_global_embed"])
     want.update(d_local_embed=lo.grad, d_global_embed=gl.grad)
-    bad = H.compare_grads(f"MLP decoder {loss} K={K} T={T} s={strength}", got, want)
+    bad = H.compare_grads(f"{tag} {loss} K={K} T={T} s={strength}", got, want)
     assert not bad, bad
+    return got
 
 
 # ------------------------------------------------------------------ whole training step
@@ -329,6 +355,10 @@ def _compare_step(tag, model, want):
 def test_training_step_at_trained_weights(name, mode, strength, dev):
     """`training_step(...).backward()` against float64 autograd over the whole oracle: eval; train mode with the YAML's dropout 0.1
     (the Philox masks, restate.PhiloxDropout on the host); and with losses_module [LaplaceNLLLoss, DiffBCE]"""
+    _training_step_check(name, mode, strength, dev)
+
+
+def _training_step_check(name, mode, strength, dev):
     from trajsde_amd import runtime
     model, cfg, batch, kw = H.trained_step_case(name, mode, strength)
     model = model.to(dev)
@@ -340,6 +370,7 @@ def test_training_step_at_trained_weights(name, mode, strength, dev):
     want_loss, want = H.oracle_full_grads(model, cfg, batch, H.TRAINED_STEP_SEED, 1.0, 0.5, **kw)
     assert abs(float(loss) - want_loss) <= (2e-5 if mode == "nll" else 1e-5) * max(1.0, abs(want_loss))
     _compare_step(f"training step {name} {mode} s={strength}", model, want)
+    return model
 
 
 @pytest.mark.parametrize("strength", STRENGTHS)
@@ -350,6 +381,12 @@ def test_vanilla_training_step_at_trained_weights(loss, strength, dev):
     from trajsde_amd.synth import synth
     K, T = 3, 12
     batch = _pad_future(synth(S=3, n=11, L=6, F=T, box=70.0, seed=91, mixed_source=True, history_dropout=0.3), T, 91)
+    _vanilla_training_step_check(batch, loss, K, T, strength, dev)
+
+
+def _vanilla_training_step_check(batch, loss, K, T, strength, dev, tag="vanilla training step"):
+    import grid_nll_restate as G
+    from trajsde_amd.models.model_base_mix import PredictionModel
     cfg = G.nll_cfg(K, T, 4, 2) if loss == "nll" else H.grid_cfg(K, T, 4, 2)
     model = _trained(PredictionModel(**cfg, init_seed=7), strength).to(dev).train()
     value = model.training_step(H.clone_batch(batch).to(dev), 0)
@@ -357,7 +394,8 @@ def test_vanilla_training_step_at_trained_weights(loss, strength, dev):
     _check_range()
     want_loss, want = G.oracle_grid_nll_grads(model, cfg, batch) if loss == "nll" else H.oracle_grid_full_grads(model, cfg, batch)
     assert abs(float(value.detach()) - want_loss) <= 1e-5 * max(1.0, abs(want_loss))
-    _compare_step(f"vanilla training step {loss} s={strength}", model, want)
+    _compare_step(f"{tag} {loss} s={strength}", model, want)
+    return model
 
 
 def test_training_step_at_strength_2_repeats_bit_for_bit(dev):
@@ -383,4 +421,99 @@ def test_training_step_at_strength_2_repeats_bit_for_bit(dev):
         assert torch.equal(cur[0], ref[0]), call
         bad = [n for n in ref[1] if not torch.equal(cur[1][n], ref[1][n])]
         assert not bad and set(cur[1]) == set(ref[1]), (call, bad[:6])
+    _check_range()
+
+
+# ------------------------------------------------------------------ irregular observation masks
+# trajsde_amd/synth.py irregular_masks: gaps and several bos per row, rows unobserved at step 20 or never, step 20 alone, agents with
+# an interior gap, ragged and empty futures -- dealt round-robin, so that the kinds share tiles and waves.  Masked GRU steps come
+# BEFORE the kept iteration here (the "masked rows pass the state through" path of encoder_bwd.hip is live and differs row by row),
+# and the agents padded at step 20 are targets of empty global segments.  The checks and the bounds are those above.
+def _finite(grads):
+    bad = [k for k, g in grads.items() if g is not None and not bool(torch.isfinite(g).all())]
+    assert not bad, bad
+
+
+def _irregular(F, seed=61, n=13):
+    from trajsde_amd.synth import irregular
+    return irregular(S=3, n=n, L=6, F=F, box=60.0, seed=seed, mixed_source=True)
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("diff_weight", [1.0, 0.0])
+def test_encoder_backward_under_irregular_masks(diff_weight, strength, dev):
+    res, got = _encoder_backward_check(_irregular(5), diff_weight, strength, dev, tag="encoder, irregular masks,")
+    _finite(got)
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("heads", [8, 4])
+def test_aggregator_backward_under_irregular_masks(heads, strength, dev):
+    _finite(_aggregator_backward_check(_irregular(5, seed=62), 3, heads, strength, dev))
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("loss", ["l2", "nll"])
+def test_decoder_backward_under_irregular_masks(loss, strength, dev):
+    """ragged futures, actors without any valid future step (observed at step 20 or not) under the SDE decoder's L2 and NLL"""
+    K, T = 4, 20
+    case = _decoder_case(3, 13, K, T, 2.0, None, strength, dev, 0, 11, 93, batch=_irregular(T, seed=63))
+    model, cfg, batch, data, y_rot, noise, local, glob, out = case
+    rt = model.decoder._rt
+    if loss == "nll":
+        res = rt.decoder_nll_backward(data, local, glob, out, noise, eps=1e-6)
+    else:
+        res = rt.decoder_l2_backward(data, local, glob, out, noise)
+    _check_range()
+    _finite(_decoder_check(f"decoder {loss}, irregular masks, K={K} T={T} s={strength}", res, model, cfg, batch, local, glob, y_rot, 93,
+                           1e-6 if loss == "nll" else None, 2e-5 if loss == "nll" else 1e-5))
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+def test_vanilla_encoder_backward_under_irregular_masks(strength, dev):
+    """padding_mask is the temporal transformer's key-padding mask: gaps inside the history, rows padded everywhere"""
+    _finite(_vanilla_encoder_backward_check(_irregular(5, seed=64), 4, 2, strength, dev, tag="vanilla encoder, irregular masks,"))
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("loss", ["l2", "nll"])
+def test_mlp_decoder_backward_under_irregular_masks(loss, strength, dev):
+    _finite(_mlp_decoder_backward_check(_irregular(12, seed=65), loss, 3, 12, strength, dev, tag="MLP decoder, irregular masks,"))
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("mode", H.TRAINED_STEP_MODES)
+def test_training_step_under_irregular_masks(mode, strength, dev):
+    model = _training_step_check("irregular_k6_t20", mode, strength, dev)
+    _finite({n: p.grad for n, p in model.named_parameters()})
+
+
+@pytest.mark.parametrize("strength", STRENGTHS)
+@pytest.mark.parametrize("loss", ["l2", "nll"])
+def test_vanilla_training_step_under_irregular_masks(loss, strength, dev):
+    model = _vanilla_training_step_check(_irregular(12, seed=66), loss, 3, 12, strength, dev,
+                                         tag="vanilla training step, irregular masks,")
+    _finite({n: p.grad for n, p in model.named_parameters()})
+
+
+def test_training_step_under_irregular_masks_repeats_bit_for_bit(dev):
+    """train mode (dropout 0.1) twice on the irregular batch at strength 2: the same loss bits and gradient words"""
+    from trajsde_amd import runtime
+    model, cfg, batch, _ = H.trained_step_case("irregular_k6_t20", "dropout", 2.0)
+    model = model.to(dev).train()
+    ref = None
+    for call in range(2):
+        model.zero_grad(set_to_none=True)
+        loss = model.training_step(H.clone_batch(batch).to(dev), 0, noise=runtime.NoiseSpec(seed=7, dropout_seed=8))
+        loss.backward()
+        torch.cuda.synchronize()
+        cur = (loss.detach().clone(), {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None})
+        if ref is None:
+            ref = cur
+            assert len(cur[1]) > 200
+            _finite(cur[1])
+            continue
+        assert torch.equal(cur[0], ref[0])
+        bad = [n for n in ref[1] if not torch.equal(cur[1][n], ref[1][n])]
+        assert not bad and set(cur[1]) == set(ref[1]), bad[:6]
     _check_range()

@@ -124,6 +124,10 @@ def _stage_check(model, cfg, batch, want, dev, tag):
         g = model.aggregator(data=data, local_embed=local32.to(dev))
         g_want = restate.global_interactor(P, c, b64, rot64, local32.double())
         errs["aggregator"] = _scaled(g.cpu(), g_want)
+        gone = batch["padding_mask"][:, c["historical_steps"] - 1].cpu()     # targets of an empty global segment: written all the same
+        if bool(gone.any()):
+            assert bool(torch.isfinite(g.cpu()[:, gone]).all())
+            errs["aggregator[padded at 20]"] = _scaled(g.cpu()[:, gone], g_want[:, gone])
         glob32 = want["global_embed"].float()
         sched = decoder_schedule(T, c["max_fut_t"], c["min_stepsize"])
         z = torch.from_numpy(np.stack([philox.normals(SEED, philox.STREAM_DECODER, k, np.arange(K * N), 64) for k in range(sched.n_euler)]))
@@ -145,6 +149,23 @@ def test_stages_in_isolation_match_float64_oracle(name, strength, dev):
     """errors cannot cancel between stages"""
     model, cfg, batch, want = _oracle(name, strength)
     _stage_check(model, cfg, batch, want, dev, f"stages {name} s={strength}")
+
+
+@pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
+@pytest.mark.parametrize("name", H.IRREGULAR_CASES)
+def test_stages_in_isolation_under_irregular_masks(name, strength, dev):
+    """_stage_check (diff_in / diff_out picked at eos[agent_index] of agents with a gap among its figures) with every device buffer
+    the stages ask for starting as NaN (tests/guarded_memory.py): the aggregate rows of the agents padded at step 20, whom no global
+    edge reaches, are the oracle's and not what the workspace held"""
+    import guarded_memory as GM
+    model, cfg, batch, want = _oracle(name, strength)
+    assert int(batch["padding_mask"][:, 20].sum()) >= 4
+    gm = GM.GuardedMemory(poison="nan")
+    with gm:
+        _stage_check(model, cfg, batch, want, dev, f"stages {name} s={strength}")
+    assert gm.routed > 0
+    rep = gm.check()
+    assert rep.ok, str(rep)
 
 
 @pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
@@ -203,7 +224,7 @@ _CHILD = (
     "from trajsde_amd.runtime import NoiseSpec\n"
     "outs = {}\n"
     "for s in H.TRAINED_STRENGTHS:\n"
-    "    m, cfg, b = W._model('mixed_k6_t20', s)\n"
+    "    m, cfg, b = W._model(sys.argv[2], s)\n"
     "    with torch.no_grad():\n"
     "        o = m.to('cuda')(b.to('cuda'), noise=NoiseSpec(seed=W.SEED))\n"
     "    _lib.check_range()\n"
@@ -211,21 +232,21 @@ _CHILD = (
     "torch.save(outs, sys.argv[1])\n")
 
 
-def _child(tmp_path, mode, env):
+def _child(tmp_path, mode, env, name="mixed_k6_t20"):
     path = str(tmp_path / (mode + ".pt"))
     script = _CHILD % (H.ROOT, os.path.join(H.ROOT, "tests"), os.path.join(H.ROOT, "oracle"))
-    subprocess.run([sys.executable, "-c", script, path], check=True, env={**os.environ, **env}, timeout=600)
+    subprocess.run([sys.executable, "-c", script, path, name], check=True, env={**os.environ, **env}, timeout=600)
     return torch.load(path)
 
 
-def _forms_against_oracle(tmp_path, modes):
-    want = {s: _oracle("mixed_k6_t20", s)[3] for s in H.TRAINED_STRENGTHS}
+def _forms_against_oracle(tmp_path, modes, name="mixed_k6_t20"):
+    want = {s: _oracle(name, s)[3] for s in H.TRAINED_STRENGTHS}
     bad = []
     for mode, env in modes:
-        got = _child(tmp_path, mode, env)
+        got = _child(tmp_path, mode, env, name)
         for s in H.TRAINED_STRENGTHS:
             errs = {k: H.maxdiff(got[s][k], want[s][k]) for k in KEYS}
-            _report(f"kernel form {mode} s={s}", errs)
+            _report(f"kernel form {mode}{'' if name == 'mixed_k6_t20' else ' ' + name} s={s}", errs)
             bad += [(mode, s, k, e) for k, e in errs.items() if e > TOL]
     assert not bad, bad
 
@@ -244,6 +265,20 @@ def test_strict24_library_matches_float64_oracle(dev, tmp_path):
     if not os.path.isfile(build.STRICT_LIB):
         pytest.skip("variants/libtrajsde_strict24.so not built")
     _forms_against_oracle(tmp_path, [("strict24", {"TRAJSDE_LIB": build.STRICT_LIB})])
+
+
+def test_every_kernel_form_under_irregular_masks(dev, tmp_path):
+    """the legacy and the cooperative recurrence, the gathering and the scene-cached global attention each carry mask code of their
+    own: the same switch matrix on the irregular batch (masked GRU steps before the kept iteration, agents without global edges)"""
+    from trajsde_amd import _lib
+    _forms_against_oracle(tmp_path, [(m, dict(e, TRAJSDE_LIB=_lib.ALT_LIB_PATH) if m in _ALT_MODES else e) for m, e in _MODES],
+                          name="irregular_k6_t20")
+
+
+def test_strict24_library_under_irregular_masks(dev, tmp_path):
+    from trajsde_amd import build
+    assert os.path.isfile(build.STRICT_LIB), "variants/libtrajsde_strict24.so not built"
+    _forms_against_oracle(tmp_path, [("strict24", {"TRAJSDE_LIB": build.STRICT_LIB})], name="irregular_k6_t20")
 
 
 @pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
@@ -271,7 +306,15 @@ def test_milstein_model(strength, dev):
     import restate
     from trajsde_amd.runtime import NoiseSpec
     from trajsde_amd.schedule import decoder_schedule, encoder_schedule
-    model, cfg, batch = _model("mixed_k6_t20", strength, method="milstein")
+    _milstein_check("mixed_k6_t20", strength, dev, f"milstein s={strength}")
+
+
+def _milstein_check(name, strength, dev, tag):
+    import milstein_restate as MR
+    import restate
+    from trajsde_amd.runtime import NoiseSpec
+    from trajsde_amd.schedule import decoder_schedule, encoder_schedule
+    model, cfg, batch = _model(name, strength, method="milstein")
     c = restate.flat_cfg(cfg)
     P = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in model.state_dict().items()}
     b64 = H.double_batch(batch)
@@ -287,7 +330,7 @@ def test_milstein_model(strength, dev):
     torch.cuda.synchronize()
     _check_range()
     errs = {k: H.maxdiff(o[k].cpu(), want[k]) for k in KEYS}
-    _report(f"milstein s={strength}", errs)
+    _report(tag, errs)
     for k, e in errs.items():
         assert e <= TOL, (k, e)
 
@@ -296,7 +339,12 @@ def test_milstein_model(strength, dev):
 def test_forward_ood(strength, dev):
     """forward_ood (MODEL:89-98, ENC:204-370): no fake agents, ten stochastic encoder passes, per-actor std"""
     from trajsde_amd.runtime import NoiseSpec
-    model, cfg, batch = _model("mixed_k6_t20", strength)
+    _ood_check("mixed_k6_t20", strength, dev, f"forward_ood s={strength}")
+
+
+def _ood_check(name, strength, dev, tag):
+    from trajsde_amd.runtime import NoiseSpec
+    model, cfg, batch = _model(name, strength)
     want = H.oracle_forward64(model, cfg, batch, noise_seed=SEED, want_intermediates=False, ood=True)
     model = model.to(dev)
     model.ood = True
@@ -305,7 +353,7 @@ def test_forward_ood(strength, dev):
     torch.cuda.synchronize()
     _check_range()
     errs = {k: H.maxdiff(o[k].cpu(), want[k]) for k in ("stds", "loc", "pi")}
-    _report(f"forward_ood s={strength}", errs)
+    _report(tag, errs)
     for k, e in errs.items():
         assert e <= TOL, (k, e)
 
@@ -318,6 +366,12 @@ def test_vanilla_grid_forward(strength, dev):
     from trajsde_amd.synth import synth
     K, T = 6, 30
     batch = synth(S=3, n=20, L=9, F=T, box=100.0, seed=720, mixed_source=True, history_dropout=0.4)
+    _grid_check(batch, K, T, strength, dev, f"grid s={strength}")
+
+
+def _grid_check(batch, K, T, strength, dev, tag):
+    import restate_grid
+    from trajsde_amd.models.model_base_mix import PredictionModel
     model = PredictionModel(**H.grid_cfg(K, T, 4, 4), init_seed=9).eval()
     H.trained_like_parameters(model, H.TRAINED_SEED, strength)
     P = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in model.state_dict().items()}
@@ -328,7 +382,7 @@ def test_vanilla_grid_forward(strength, dev):
     _check_range()
     errs = {k: H.maxdiff(o[k].cpu(), want[k]) for k in ("loc", "pi")}
     errs.update({k: _scaled(o[k].cpu(), want[k]) for k in ("local_embed", "global_embed")})
-    _report(f"grid s={strength}", errs)
+    _report(tag, errs)
     for k, e in errs.items():
         assert e <= TOL, (k, e)
 
@@ -338,7 +392,13 @@ def test_training_forward(strength, dev):
     """the tape-keeping kernels of a training step (dropout 0) at the profile: their outputs against the oracle"""
     from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet
     from trajsde_amd.runtime import NoiseSpec
-    K, T, max_t, make = H.TRAINED_CASES["mixed_k6_t20"]
+    _training_forward_check("mixed_k6_t20", strength, dev, f"training forward s={strength}")
+
+
+def _training_forward_check(name, strength, dev, tag):
+    from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet
+    from trajsde_amd.runtime import NoiseSpec
+    K, T, max_t, make = H.TRAINED_CASES[name]
     cfg = H.our_cfg(K, T, max_t)
     cfg["encoder"]["kwargs"]["dropout"] = cfg["aggregator"]["kwargs"]["dropout"] = 0.0
     model = PredictionModelSDENet(**cfg, init_seed=2)
@@ -353,7 +413,7 @@ def test_training_forward(strength, dev):
     assert enc_tape is not None and agg_tape is not None
     errs = {k: H.maxdiff(out[k].detach().cpu(), want[k]) for k in KEYS}
     errs.update(local_embed=_scaled(local.detach().cpu(), want["local_embed"]), global_embed=_scaled(glob.detach().cpu(), want["global_embed"]))
-    _report(f"training forward s={strength}", errs)
+    _report(tag, errs)
     for k, e in errs.items():
         assert e <= TOL, (k, e)
 
@@ -386,3 +446,55 @@ def test_weight_reload_and_graph_replay(dev):
     got = {k: gf(seed=SEED)[k].clone() for k in KEYS}
     for k in KEYS:
         assert torch.equal(got[k], b[k]), k
+
+
+# ----------------------------------------------------------------------------- irregular observation masks (synth.irregular_masks)
+# test_forward_matches_float64_oracle runs both H.IRREGULAR_CASES through CASES; the entry points below have mask code of their own
+@pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
+def test_forward_ood_under_irregular_masks(strength, dev):
+    """forward_ood's own recurrence loop: masked steps before the kept iteration, rows without a bos"""
+    _ood_check("irregular_k6_t20", strength, dev, f"forward_ood irregular_k6_t20 s={strength}")
+
+
+@pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
+def test_training_forward_under_irregular_masks(strength, dev):
+    _training_forward_check("irregular_k6_t20", strength, dev, f"training forward irregular_k6_t20 s={strength}")
+
+
+@pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
+def test_milstein_model_under_irregular_masks(strength, dev):
+    _milstein_check("irregular_k6_t20", strength, dev, f"milstein irregular_k6_t20 s={strength}")
+
+
+@pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
+def test_vanilla_grid_forward_under_irregular_masks(strength, dev):
+    """padding_mask as the temporal transformer's key-padding mask: gaps inside the history, rows padded at every step"""
+    from trajsde_amd.synth import irregular
+    _grid_check(irregular(S=3, n=13, L=6, F=12, box=80.0, seed=42, mixed_source=True), 3, 12, strength, dev, f"grid, irregular masks, s={strength}")
+
+
+@pytest.mark.parametrize("strength", H.TRAINED_STRENGTHS)
+def test_bf16_state_storage_under_irregular_masks(strength, dev):
+    """`set_state_storage("bf16")` on the irregular batch at that storage form's own bound (test_gpu_parity.
+    test_stress_shape_config5_fp32_and_bf16_state: finite, within 5e-2 of the fp32-state forward on positions and scales, really
+    switched on, and the fp32 path bit for bit itself once the switch is back)"""
+    from trajsde_amd import runtime
+    from trajsde_amd.runtime import NoiseSpec
+    model, cfg, batch, want = _oracle("irregular_k6_t20", strength)
+    model = model.to(dev)
+    with torch.no_grad():
+        o32 = model(H.clone_batch(batch).to(dev), noise=NoiseSpec(seed=SEED))
+        prev = runtime.set_state_storage("bf16")
+        try:
+            o16 = model(H.clone_batch(batch).to(dev), noise=NoiseSpec(seed=SEED))
+            torch.cuda.synchronize()
+        finally:
+            runtime.set_state_storage(prev)
+        again = model(H.clone_batch(batch).to(dev), noise=NoiseSpec(seed=SEED))
+    assert torch.isfinite(o16["loc"]).all() and torch.isfinite(o16["pi"]).all()
+    d_xy = H.maxdiff(o16["loc"][..., :2].cpu(), o32["loc"][..., :2].cpu())
+    d_sc = H.maxdiff(o16["loc"][..., 2:].cpu(), o32["loc"][..., 2:].cpu())
+    _report(f"bf16 state irregular_k6_t20 s={strength}", {"xy": d_xy, "scale": d_sc, "fp32 loc": H.maxdiff(o32["loc"].cpu(), want["loc"])})
+    assert 0.0 < d_xy <= 5e-2, d_xy
+    assert d_sc <= 5e-2, d_sc
+    assert torch.equal(again["loc"], o32["loc"]) and torch.equal(again["pi"], o32["pi"])

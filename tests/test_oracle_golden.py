@@ -28,20 +28,12 @@ def test_restatement_matches_reference_golden(name):
 
 
 def _load_ood(name="ood_k3_t5"):
-    import os
-    from trajsde_amd.data import TemporalData
-    z = np.load(os.path.join(H.ROOT, "tests", "golden_ood", name + ".npz"))
-    batch = TemporalData(**{k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in.")})
-    batch["num_nodes"] = batch["x"].shape[0]
-    meta = {k[5:]: z[k].item() for k in z.files if k.startswith("meta.")}
-    out = {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("out.")}
-    return batch, meta, out
+    return H.load_ood_fixture(name)
 
 
-def test_restatement_matches_reference_golden_ood():
-    """MODEL:89-98 with ood=True (forward_ood, ENC:204-370), golden from the reference itself."""
+def _ood_restatement(name):
     import restate
-    batch, meta, out = _load_ood()
+    batch, meta, out = _load_ood(name)
     model, cfg = H.build_model(meta)
     P = {k: v.detach().clone() for k, v in model.state_dict().items()}
     mine = restate.forward(P, cfg, H.clone_batch(batch), restate.PhiloxNoise(int(meta["noise_seed"])), ood=True)
@@ -49,7 +41,34 @@ def test_restatement_matches_reference_golden_ood():
         assert H.maxdiff(mine[key], out[key]) <= 1e-5, key
 
 
+def test_restatement_matches_reference_golden_ood():
+    """MODEL:89-98 with ood=True (forward_ood, ENC:204-370), golden from the reference itself."""
+    _ood_restatement("ood_k3_t5")
+
+
+def test_restatement_matches_reference_golden_ood_under_irregular_masks():
+    """forward_ood's own recurrence loop on synth.irregular_masks rows: masked steps before the kept iteration, rows without a bos"""
+    _ood_restatement("ood_irregular_k3_t5")
+
+
+def test_irregular_fixtures_hold_every_row_kind():
+    """the reference-made irregular fixtures were made on the hard rows (synth.irregular_masks asserts this of what it returns; here of
+    what was committed): every kind and a row observed at step 20 without any valid future step at least twice, agents with two bos"""
+    from trajsde_amd.synth import T_HIST, mask_categories
+    batches = [H.load_fixture("irregular_k3_t12")[0], H.load_ood_fixture("ood_irregular_k3_t5")[0],
+               H.load_train_fixture("train_irregular_k3_t12")[0], H.load_train_fixture("train_grid_irregular_k3_t12_h4")[0]]
+    z = H.load_grid_arrays("grid_irregular_k3_t12_h4")
+    batches.append({k[3:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("in.")})
+    for b in batches:
+        cat = mask_categories(b)
+        pm, bos = b["padding_mask"], b["bos_mask"]
+        assert int(cat.min()) >= 0 and int(torch.bincount(cat, minlength=5).min()) >= 2
+        assert int((~pm[:, T_HIST - 1] & pm[:, T_HIST:].all(1)).sum()) >= 2
+        assert bool((bos[b["agent_index"]].sum(1) >= 2).all()) and not bool(pm[b["agent_index"], T_HIST - 1].any())
+
+
 GRID = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(H.ROOT, "tests", "golden_grid", "*.npz")))
+GRID.append("grid_irregular_k3_t12_h4")                      # tests/golden/irregular_grid
 
 
 @pytest.mark.parametrize("name", GRID)
@@ -60,8 +79,8 @@ def test_vanilla_restatement_matches_reference_golden(name):
     import yaml
     from trajsde_amd.data import TemporalData
     from trajsde_amd.models.model_base_mix import PredictionModel
-    z = np.load(os.path.join(H.ROOT, "tests", "golden_grid", name + ".npz"))
-    batch = TemporalData(**{k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in.")})
+    z = H.load_grid_arrays(name)
+    batch = TemporalData(**{k[3:]: torch.from_numpy(v) for k, v in z.items() if k.startswith("in.")})
     with open(os.path.join(H.ROOT, "trajsde_amd/configs/mi355x_trmenc_mlpdec.yml")) as f:
         cfg = yaml.safe_load(f)
     K, T, heads, layers = (int(z["meta." + k]) for k in ("num_modes", "future_steps", "num_heads", "num_temporal_layers"))
@@ -69,7 +88,7 @@ def test_vanilla_restatement_matches_reference_golden(name):
     cfg["encoder"]["kwargs"].update(num_heads=heads, num_temporal_layers=layers)
     cfg["aggregator"]["kwargs"].update(num_modes=K, num_heads=heads)
     cfg["decoder"]["kwargs"].update(num_modes=K, future_steps=T)
-    if "meta.uncertain" in z.files and int(z["meta.uncertain"]) == 0:      # the decoder without its scale head (GDEC:31, :58-59)
+    if "meta.uncertain" in z and int(z["meta.uncertain"]) == 0:      # the decoder without its scale head (GDEC:31, :58-59)
         cfg["decoder"]["kwargs"]["uncertain"] = False
     model = PredictionModel(**cfg, init_seed=int(z["meta.init_seed"]))
     sd = model.state_dict()
