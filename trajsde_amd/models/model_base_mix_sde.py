@@ -7,46 +7,15 @@ on `data` (MODEL:83-85), `validation_step/test_step` feeding the same metric for
 `pytorch_lightning.LightningModule` wherever that package is importable (what `pl.Trainer.fit / test` of train.py:54-66,
 test.py:58 require of the model class) and a plain nn.Module in this image, where it is not and trajsde_amd.driver spells
 the loops out (models/lightning_base.py); `test_epoch_end`, `only_agent` / `leave_only_agent` and the `self.log` calls
-of the reference's steps are there under both.
+of the reference's steps are there under both.  What this model shares with the vanilla HiVT one (model_base_mix.py) -- the
+constructor, the evaluation steps, the torch side of the cotangent route, `GradSet`, `resolve_class` -- is models/glue_base.py.
 """
-import os
-from copy import deepcopy
-from importlib.machinery import SourceFileLoader
 from typing import Optional
 
 import torch
-import torch.nn as nn
 
 from trajsde_amd import runtime
-from trajsde_amd.models.lightning_base import LightningHooks
-
-_REPO_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def resolve_class(file_path: str, module_name: str):
-    """The reference's registry: getattr(SourceFileLoader(name, path).load_module(name), name)."""
-    path = file_path if os.path.isfile(file_path) else os.path.join(_REPO_ROOT, file_path)
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"stage file '{file_path}' not found (cwd or {_REPO_ROOT})")
-    return getattr(SourceFileLoader(module_name, path).load_module(module_name), module_name)
-
-
-class GradSet:
-    """the three stages' gradient buffers of one training step: (name prefix, runtime.GradBuffers, multiplier) each.  The training
-    loop's sink takes them whole (driver.FlatGrads.accumulate_bundles); `by_name()` spells them out per parameter for everyone else."""
-
-    def __init__(self) -> None:
-        self.bundles = []
-
-    def add(self, prefix: str, grads, mult: float = 1.0) -> None:
-        self.bundles.append((prefix, grads, float(mult)))
-
-    def by_name(self) -> dict:
-        out = {}
-        for prefix, grads, mult in self.bundles:
-            for n, g in grads.items():
-                out[prefix + n] = g if mult == 1.0 else g * mult
-        return out
+from trajsde_amd.models.glue_base import GlueBase, GradSet, resolve_class  # noqa: F401  (resolve_class: imported from here by the driver and tests)
 
 
 class _PathLoss(torch.autograd.Function):
@@ -108,48 +77,7 @@ class _PathLoss(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(None if x is None else next(scaled) for x in ctx.grads)
 
 
-class PredictionModelSDENet(LightningHooks):
-    def __init__(self, **kwargs) -> None:
-        super().__init__()
-        self._record_hparams(kwargs)                                      # MODEL:28 save_hyperparameters()
-        init_seed: Optional[int] = kwargs.get("init_seed")
-        for key, value in kwargs.items():
-            if key == "training_specific":
-                for k, v in value.items():
-                    setattr(self, k, v)
-            elif key == "model_specific":
-                for k, v in value["kwargs"].items():
-                    setattr(self, k, v)
-
-        def build(section, offset):
-            args = kwargs[section]
-            kw = dict(args["kwargs"])
-            if init_seed is not None:
-                kw["init_seed"] = init_seed + offset
-            return resolve_class(args["file_path"], args["module_name"])(**kw)
-
-        self.encoder = build("encoder", 1)
-        self.aggregator = build("aggregator", 2)
-        self.decoder = build("decoder", 3)
-
-        self.losses, self.loss_names = [], []
-        for i, path in enumerate(kwargs.get("losses", [])):
-            name = kwargs["losses_module"][i]
-            self.losses.append(resolve_class(path, name)(**dict(kwargs["loss_args"][i])))
-            self.loss_names.append(name)
-        self.loss_weights = kwargs.get("loss_weights", [])
-        self.metrics_tr, self.metrics_vl, self.metric_names = [], [], []
-        for i, path in enumerate(kwargs.get("metrics", [])):
-            name = kwargs["metrics_module"][i]
-            metric = resolve_class(path, name)(**dict(kwargs["metric_args"][i]))
-            self.metrics_tr.append(metric)
-            self.metrics_vl.append(deepcopy(metric))
-            self.metric_names.append(name)
-
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
+class PredictionModelSDENet(GlueBase):
     def forward(self, data, noise: Optional["runtime.NoiseSpec"] = None, preserve_side_effects: Optional[bool] = None):
         """MODEL:74-102.  `noise` (optional, ours) selects the Philox seed or injected normals; the default
         draws a fresh Philox seed from torch's global generator, like the reference draws fresh noise.
@@ -160,14 +88,9 @@ class PredictionModelSDENet(LightningHooks):
             preserve_side_effects = getattr(self, "preserve_side_effects", None)
         ood = bool(getattr(self, "ood", False))                              # test.py --ood injects this flag (test.py:45-46)
         noise = runtime.NoiseSpec.resolve(noise)
-        if self.rotate:
-            if not runtime.consume_rotation(data):
-                rotate_mat, y_rot = runtime.rotate_inputs(data)          # MODEL:76-85
-                if y_rot is not None:
-                    data.y = y_rot
-                data["rotate_mat"] = rotate_mat
-        else:
+        if not self.rotate:
             raise NotImplementedError("rotate=False is not built (shipped config: rotate: true, CFG:18)")
+        self._ensure_rotated(data)                                           # MODEL:76-85
         prepared = None
         if ood:
             local_embed, stds = self.encoder.forward_ood(data=data, noise=noise)            # MODEL:89-90
@@ -195,14 +118,6 @@ class PredictionModelSDENet(LightningHooks):
         from trajsde_amd import _lib
         _lib.check_range()
 
-    def _regression_loss(self):
-        """(name, eps) of the configured regression loss: "L2" (losses/L2.py, the shipped one) or "LaplaceNLLLoss"
-        (losses/laplace_nll_loss.py: the scale head is trained as well)"""
-        for name, fn in zip(self.loss_names, self.losses):
-            if name == "LaplaceNLLLoss":
-                return name, float(getattr(fn, "eps", 1e-6))
-        return "L2", None
-
     def _cotangent_route(self) -> bool:
         """True when the configured loss set is not one the fused backward entry points differentiate ({L2 | LaplaceNLLLoss}
         (+ DiffBCE)): `training_step` then evaluates every loss except DiffBCE as the torch callable it is and hands dL/dloc, dL/dpi
@@ -213,20 +128,15 @@ class PredictionModelSDENet(LightningHooks):
         unknown = set(self.loss_names) - {"L2", "LaplaceNLLLoss", "DiffBCE"}
         return bool(unknown or self._regression_loss()[0] not in weights or ("L2" in weights and "LaplaceNLLLoss" in weights))
 
-    def params_with_gradient(self):
-        """the parameters the configured losses reach (under L2 / LaplaceNLLLoss everything except the decoder's pi / scale heads
-        and unused buffers-as-parameters: the reference's autograd leaves the others' `.grad` at None, so AdamW skips them; a loss set
-        on the cotangent route reaches `decoder.scale.*` and `decoder.pi.*` too)"""
+    def _backward_stage_ids(self):
+        """under L2 / LaplaceNLLLoss the tables leave out the decoder's pi / scale heads and unused buffers-as-parameters; a loss set
+        on the cotangent route reaches `decoder.scale.*` and `decoder.pi.*` too"""
         from trajsde_amd import _lib
-        reached = set()
         if self._cotangent_route():
             dec_stage = _lib.STAGE_DECODER_COT_BWD
         else:
             dec_stage = _lib.STAGE_DECODER_NLL_BWD if self._regression_loss()[0] == "LaplaceNLLLoss" else _lib.STAGE_DECODER_BWD
-        for stage, sid in (("encoder", _lib.STAGE_ENCODER_BWD), ("aggregator", _lib.STAGE_AGGREGATOR_BWD),
-                           ("decoder", dec_stage)):
-            reached |= {f"{stage}.{n}" for n in getattr(self, stage)._rt.param_names(sid)}
-        return [p for n, p in self.named_parameters() if n in reached]
+        return _lib.STAGE_ENCODER_BWD, _lib.STAGE_AGGREGATOR_BWD, dec_stage
 
     def _loss_and_gradients(self, data, noise, w_l2: float, w_diff: float):
         """the HIP forward and, right behind it, the three stage backward entry points of the C-ABI (decoder -> aggregator ->
@@ -262,83 +172,59 @@ class PredictionModelSDENet(LightningHooks):
             self.__dict__["_pack_set_obj"] = ps
         return ps
 
-    def _loss_and_gradients_cotangent(self, data, noise, w_diff: float):
-        """the step of a loss set on the cotangent route: tape-keeping forward; every configured loss except DiffBCE evaluated as
-        the torch callable it is on detached `loc` / `pi` leaves; dL/dloc and dL/dpi from torch.autograd.grad; then the decoder's
-        cotangent backward, the aggregator's and the encoder's (DiffBCE stays inside the latter, through `diff_weight`)"""
+    def _loss_and_gradients_pinned(self, data, noise, w_l2: float, w_diff: float):
+        """one forward per step: the encoder and aggregator run their tape-keeping forward, the backward entry points then walk
+        those tapes instead of recomputing the stage (runtime.*_forward_train).  The decoder step is the welded entry point of the
+        configured regression loss, scaled by `w_l2` -- or, on the cotangent route, every configured loss except DiffBCE evaluated by
+        torch on detached `loc` / `pi` leaves and dL/dloc, dL/dpi handed to the decoder's cotangent backward.  DiffBCE stays inside
+        the encoder backward on both, through `diff_weight`."""
         enc_rt, agg_rt, dec_rt = self.encoder._rt, self.aggregator._rt, self.decoder._rt
+        custom = self._cotangent_route()
         out, local, glob, enc_tape, agg_tape = self._forward_stages(data, noise, keep_tapes=True)
-        loc = out["loc"].detach().requires_grad_(True)
-        pi = out["pi"].detach().requires_grad_(True)
-        view = dict(out)
-        view["loc"], view["pi"] = loc, pi
-        values, total = {}, None
-        with torch.enable_grad():
-            for name, fn, w in zip(self.loss_names, self.losses, self.loss_weights):
-                if name == "DiffBCE":
-                    continue
-                v = fn(data, view)
-                values[name] = v.detach()
-                total = v * float(w) if total is None else total + v * float(w)
-            d_loc = d_pi = None
-            if total is not None and total.requires_grad:
-                d_loc, d_pi = torch.autograd.grad(total, [loc, pi], allow_unused=True)
-        dec = dec_rt.decoder_cotangent_backward(data, local, glob, out, noise, d_loc, d_pi)
-        agg = agg_rt.aggregator_backward(data, local, dec["d_global_embed"], noise, tape=agg_tape)
+        if custom:
+            values, total, d_loc, d_pi = self._torch_losses(data, out, skip=("DiffBCE",))
+            dec = dec_rt.decoder_cotangent_backward(data, local, glob, out, noise, d_loc, d_pi)
+            w_dec = 1.0                                       # (the loss weights are inside dL/dloc and dL/dpi)
+        else:
+            reg, eps = self._regression_loss()
+            if reg == "LaplaceNLLLoss":
+                dec = dec_rt.decoder_nll_backward(data, local, glob, out, noise, eps=eps)
+            else:
+                dec = dec_rt.decoder_l2_backward(data, local, glob, out, noise)
+            w_dec = w_l2
+        d_glob, d_local = dec["d_global_embed"], dec["d_local_embed"]
+        if w_dec != 1.0:
+            d_glob, d_local = d_glob * w_dec, d_local * w_dec
+        agg = agg_rt.aggregator_backward(data, local, d_glob, noise, tape=agg_tape)
         del agg_tape
         gs = GradSet()
-        gs.add("decoder.", dec["grads"])
+        gs.add("decoder.", dec["grads"], w_dec)
         gs.add("aggregator.", agg["grads"])
-        sink = getattr(self, "_grad_sink", None)
-        if sink is not None and getattr(sink, "early_enabled", False) and self._direct_accumulation():
-            if not (hasattr(sink, "early_reduce_bundles") and sink.early_reduce_bundles(gs.bundles)):
-                early = gs.by_name()
-                named = dict(self.named_parameters())
-                sink.early_reduce([named[n] for n in early], [early[n] for n in early])
-        enc = enc_rt.encoder_backward(data, dec["d_local_embed"] + agg["d_local_embed"], noise, diff_weight=w_diff, tape=enc_tape)
+        self._early_reduce(gs)
+        enc = enc_rt.encoder_backward(data, d_local + agg["d_local_embed"], noise, diff_weight=w_diff, tape=enc_tape)
         del enc_tape
         gs.add("encoder.", enc["grads"])
         self.last_output = out
-        self.last_losses = dict(values)
-        if "DiffBCE" in self.loss_names:
-            self.last_losses["DiffBCE"] = enc["diff_loss"].detach() / w_diff if w_diff else None
-        value = enc["diff_loss"] if total is None else total.detach() + enc["diff_loss"]
+        diff = enc["diff_loss"].detach() / w_diff if w_diff else None
+        if custom:
+            self.last_losses = dict(values)
+            if "DiffBCE" in self.loss_names:
+                self.last_losses["DiffBCE"] = diff
+            value = enc["diff_loss"] if total is None else total.detach() + enc["diff_loss"]
+        else:
+            self.last_losses = {reg: dec["loss"].detach(), "DiffBCE": diff}
+            value = w_l2 * dec["loss"] + enc["diff_loss"]
         return value.clone(), gs
 
-    def _loss_and_gradients_pinned(self, data, noise, w_l2: float, w_diff: float):
-        if self._cotangent_route():
-            return self._loss_and_gradients_cotangent(data, noise, w_diff)
-        enc_rt, agg_rt, dec_rt = self.encoder._rt, self.aggregator._rt, self.decoder._rt
-        reg = self._regression_loss()
-        # one forward per step: the encoder and aggregator run their tape-keeping forward, the backward entry points
-        # then walk those tapes instead of recomputing the stage (runtime.*_forward_train)
-        out, local, glob, enc_tape, agg_tape = self._forward_stages(data, noise, keep_tapes=True)
-        if reg[0] == "LaplaceNLLLoss":
-            dec = dec_rt.decoder_nll_backward(data, local, glob, out, noise, eps=reg[1])
-        else:
-            dec = dec_rt.decoder_l2_backward(data, local, glob, out, noise)
-        d_glob, d_local = dec["d_global_embed"], dec["d_local_embed"]
-        if w_l2 != 1.0:
-            d_glob, d_local = d_glob * w_l2, d_local * w_l2
-        agg = agg_rt.aggregator_backward(data, local, d_glob, noise, tape=agg_tape)
-        del agg_tape
-        # multi-rank training loop (driver.train): the decoder's and aggregator's gradients are final -- their slice of the flat
-        # gradient buffer goes to the all-reduce now, on the collective stream, under the encoder backward (driver.FlatGrads)
-        gs = GradSet()
-        gs.add("decoder.", dec["grads"], w_l2)
-        gs.add("aggregator.", agg["grads"])
+    def _early_reduce(self, gs: GradSet) -> None:
+        """multi-rank training loop (driver.train): the decoder's and aggregator's gradients are final -- their slice of the flat
+        gradient buffer goes to the all-reduce now, on the collective stream, under the encoder backward (driver.FlatGrads)"""
         sink = getattr(self, "_grad_sink", None)
         if sink is not None and getattr(sink, "early_enabled", False) and self._direct_accumulation():
             if not (hasattr(sink, "early_reduce_bundles") and sink.early_reduce_bundles(gs.bundles)):
                 early = gs.by_name()                                         # (a sink without the whole-buffer entry points)
                 named = dict(self.named_parameters())
                 sink.early_reduce([named[n] for n in early], [early[n] for n in early])
-        enc = enc_rt.encoder_backward(data, d_local + agg["d_local_embed"], noise, diff_weight=w_diff, tape=enc_tape)
-        del enc_tape
-        gs.add("encoder.", enc["grads"])
-        self.last_output = out
-        self.last_losses = {reg[0]: dec["loss"].detach(), "DiffBCE": enc["diff_loss"].detach() / w_diff if w_diff else None}
-        return (w_l2 * dec["loss"] + enc["diff_loss"]).clone(), gs
 
     def prefetch_graph(self, data, noise: "runtime.NoiseSpec", main_stream=None) -> None:
         """prepare `data` for the training_step that will follow with the same `noise`: rotation + graph stage on the side stream
@@ -350,11 +236,7 @@ class PredictionModelSDENet(LightningHooks):
     def _forward_stages(self, data, noise, keep_tapes: bool = False):
         """forward() that also hands back the two stage boundaries the backward entry points need; with `keep_tapes` the
         encoder and the aggregator run their tape-keeping forward and the tapes are returned too"""
-        if not runtime.consume_rotation(data):               # (done ahead of time by prefetch_graph)
-            rotate_mat, y_rot = runtime.rotate_inputs(data)
-            if y_rot is not None:
-                data.y = y_rot
-            data["rotate_mat"] = rotate_mat
+        self._ensure_rotated(data)
         enc_tape = agg_tape = None
         if keep_tapes:
             (local_embed, diff_in, diff_out, label_in, label_out), enc_tape = self.encoder._rt.encoder_forward_train(data, noise)
@@ -418,40 +300,13 @@ class PredictionModelSDENet(LightningHooks):
             params = [p for p in params if p.requires_grad][:1]
             self.__dict__["_one_param"] = params[0] if params else None
         loss = _PathLoss.apply(self, data, noise, 1.0 if custom else float(weights[reg_name]), float(weights.get("DiffBCE", 0.0)), *params)
-        n_rows = int(self.last_output["loc"].size(1))
-        for name in self.loss_names:                                          # MODEL:112: one entry per configured loss
-            if self.last_losses.get(name) is not None:
-                self.log_value(f"train/{name}", self.last_losses[name], prog_bar=True, on_step=True, on_epoch=True, batch_size=n_rows)
-        lr = self.current_lr()
-        if lr is not None:                                                    # MODEL:113 (once configure_optimizers has run)
-            self.log_value("lr", lr, prog_bar=False, on_step=False, on_epoch=True, batch_size=1)
+        self._log_training_step()
         return loss
 
-    def _agent_eval_tensors(self, data, output):
-        idx = data["agent_index"]
-        return output["loc"][:, idx, :, :2], data.y[idx], output["reg_mask"][idx], data["source"]
-
-    def validation_step(self, data, batch_idx):
-        output = self(data)
-        y_hat, y, mask, source = self._agent_eval_tensors(data, output)
-        if not self.is_gtabs:
+    def _validation_trajectories(self, y_hat, y):
+        if not self.is_gtabs:                                                 # MODEL:125-127: displacements -> positions
             y_hat, y = torch.cumsum(y_hat, dim=-2), torch.cumsum(y, dim=-2)
-        for metric in self.metrics_vl:
-            metric.update(y_hat.detach(), y.detach(), mask.detach(), source.detach())
-        return output
-
-    def test_step(self, data, batch_idx):
-        output = self(data)
-        if getattr(self, "only_agent", False):                                # MODEL:136-137
-            self.leave_only_agent(data, output)
-        if data.y is not None:
-            y_hat, y, mask, source = self._agent_eval_tensors(data, output)
-            for metric in self.metrics_vl:
-                metric.update(y_hat.detach(), y.detach(), mask.detach(), source.detach())
-        return output
-
-    def metric_results(self):
-        return {n: float(m.compute()) for n, m in zip(self.metric_names, self.metrics_vl)}
+        return y_hat, y
 
     def configure_optimizers(self):
         """AdamW + per-epoch cosine annealing (MODEL:204-207)."""

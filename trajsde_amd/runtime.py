@@ -609,6 +609,60 @@ class StageRuntime:
             self._blobs[sid] = (blob, stamp, None, packed_on)
 
     # ---------------------------------------------------------------- decoder
+    def _decoder_tables(self, T: int, dev):
+        """(EulerSchedule, step table, output table) of the SDE decoder's time grid on `dev`, cached per grid"""
+        m = self.module
+        return _TABLES.get(("dec", T, float(m.max_fut_t), float(m.min_stepsize)),
+                           lambda: decoder_schedule(T, float(m.max_fut_t), float(m.min_stepsize)), dev)
+
+    @staticmethod
+    def _targets_and_mask(data, out: Dict[str, torch.Tensor], N: int, T: int, what: str):
+        """(float32 targets [N,T,2], `reg_mask` as bytes) of the welded losses; `what`: how the error names the targets"""
+        y = data["y"]
+        if y is None or tuple(y.shape) != (N, T, 2):
+            raise _lib.TrajsdeError(f"data['y'] must be [{N},{T},2] ({what})")
+        return y.to(torch.float32).contiguous(), out["reg_mask"].contiguous().view(torch.uint8)
+
+    def _backward_outputs(self, stage_id: int, N: int, K: int, dev):
+        """what every decoder backward writes: (names, zeroed GradBuffers, their pointer array, d_local [N,64], d_global [K,N,64])"""
+        names = self.param_names(stage_id)
+        grads = self._grad_buffers(stage_id)
+        arr, grads.pointer_keep = grads.pointer_array()                      # (the addresses live as long as the buffers)
+        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
+        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
+        return names, grads, arr, d_local, d_global
+
+    @staticmethod
+    def _cotangents(d_loc: Optional[torch.Tensor], d_pi: Optional[torch.Tensor], K: int, N: int, T: int, dev, allow_two_channels: bool):
+        """caller-supplied dL/dloc, dL/dpi -> contiguous float32 [K,N,T,4] and [N,K] on `dev`; None is zeros.  `allow_two_channels`:
+        a [K,N,T,2] `d_loc` (the output of `uncertain: False`) is accepted and padded with zero scale channels"""
+        if d_loc is None:
+            d_loc4 = torch.zeros(K, N, T, 4, device=dev, dtype=torch.float32)
+        else:
+            if tuple(d_loc.shape) != (K, N, T, 4) and not (allow_two_channels and tuple(d_loc.shape) == (K, N, T, 2)):
+                hint = " (or ...,2 without the scale channels)" if allow_two_channels else ""
+                raise _lib.TrajsdeError(f"d_loc must be [{K},{N},{T},4]{hint}, got {tuple(d_loc.shape)}")
+            d_loc4 = d_loc.detach().to(device=dev, dtype=torch.float32)
+            if d_loc4.shape[-1] == 2:                       # `uncertain: False`: no scale channels came out, none carry gradient
+                d_loc4 = torch.cat([d_loc4, torch.zeros_like(d_loc4)], dim=-1)
+            d_loc4 = d_loc4.contiguous()
+        if d_pi is None:
+            d_pi_c = torch.zeros(N, K, device=dev, dtype=torch.float32)
+        else:
+            if tuple(d_pi.shape) != (N, K):
+                raise _lib.TrajsdeError(f"d_pi must be [{N},{K}], got {tuple(d_pi.shape)}")
+            d_pi_c = d_pi.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return d_loc4, d_pi_c
+
+    @staticmethod
+    def _checked_ws_bytes(query: str, *args) -> int:
+        """a workspace query that can refuse its arguments (a negative size, the reason in trajsde_last_error)"""
+        L = _lib.lib()
+        ws_bytes = getattr(L, query)(*args)
+        if ws_bytes < 0:
+            raise _lib.TrajsdeError(f"{query}: {L.trajsde_last_error().decode()}")
+        return ws_bytes
+
     def decoder_forward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor,
                         noise: Optional[NoiseSpec] = None) -> Dict[str, torch.Tensor]:
         m = self.module
@@ -617,8 +671,7 @@ class StageRuntime:
         dev = local_embed.device
         K, T = int(m.num_modes), int(m.future_steps)
         N = local_embed.shape[0]
-        sched, step_tab, out_tab = _TABLES.get(("dec", T, float(m.max_fut_t), float(m.min_stepsize)),
-                                               lambda: decoder_schedule(T, float(m.max_fut_t), float(m.min_stepsize)), dev)
+        sched, step_tab, out_tab = self._decoder_tables(T, dev)
         if noise.z_dec is not None and tuple(noise.z_dec.shape) != (sched.n_euler, K * N, D):
             raise _lib.TrajsdeError(f"z_dec must be [{sched.n_euler},{K * N},{D}] (one increment per Euler step, App. D)")
         L = _lib.lib()
@@ -671,28 +724,19 @@ class StageRuntime:
         dev = local_embed.device
         K, T = int(m.num_modes), int(m.future_steps)
         N = local_embed.shape[0]
-        sched, step_tab, out_tab = _TABLES.get(("dec", T, float(m.max_fut_t), float(m.min_stepsize)),
-                                               lambda: decoder_schedule(T, float(m.max_fut_t), float(m.min_stepsize)), dev)
-        y = data["y"]
-        if y is None or tuple(y.shape) != (N, T, 2):
-            raise _lib.TrajsdeError(f"data['y'] must be [{N},{T},2] (rotated targets, MODEL:83-84)")
-        y = y.to(torch.float32).contiguous()
-        mask = out["reg_mask"].contiguous().view(torch.uint8)
+        sched, step_tab, out_tab = self._decoder_tables(T, dev)
+        y, mask = self._targets_and_mask(data, out, N, T, "rotated targets, MODEL:83-84")
         L = _lib.lib()
         stage = _lib.STAGE_DECODER_BWD if nll_eps is None else _lib.STAGE_DECODER_NLL_BWD
-        names = self.param_names(stage)
-        grads = self._grad_buffers(stage)
+        names, grads, arr, d_local, d_global = self._backward_outputs(stage, N, K, dev)
         milstein = m.method == "milstein"
         if milstein:                       # (the same parameter tables: the gradient buffers and their order are the Euler ones)
             fwd_stage = _lib.STAGE_DECODER_MILSTEIN
             blob_stage = _lib.STAGE_DECODER_MILSTEIN_BWD if nll_eps is None else _lib.STAGE_DECODER_MILSTEIN_NLL_BWD
         else:
             fwd_stage, blob_stage = self.stage_id, stage
-        arr, _keep = grads.pointer_array()
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         best = torch.empty(N, device=dev, dtype=torch.int32)
-        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
-        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
         cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
         head = (N, K, T, self.blob(fwd_stage).data_ptr(), self.blob(blob_stage).data_ptr(),
                 local_embed.contiguous().data_ptr(), global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler,
@@ -732,35 +776,14 @@ class StageRuntime:
         dev = local_embed.device
         K, T = int(m.num_modes), int(m.future_steps)
         N = local_embed.shape[0]
-        sched, step_tab, out_tab = _TABLES.get(("dec", T, float(m.max_fut_t), float(m.min_stepsize)),
-                                               lambda: decoder_schedule(T, float(m.max_fut_t), float(m.min_stepsize)), dev)
+        sched, step_tab, out_tab = self._decoder_tables(T, dev)
         loc4 = _loc4(out)
-        if d_loc is None:
-            d_loc4 = torch.zeros(K, N, T, 4, device=dev, dtype=torch.float32)
-        else:
-            if tuple(d_loc.shape) not in ((K, N, T, 4), (K, N, T, 2)):
-                raise _lib.TrajsdeError(f"d_loc must be [{K},{N},{T},4] (or ...,2 without the scale channels), got {tuple(d_loc.shape)}")
-            d_loc4 = d_loc.detach().to(device=dev, dtype=torch.float32)
-            if d_loc4.shape[-1] == 2:                       # `uncertain: False`: no scale channels came out, none carry gradient
-                d_loc4 = torch.cat([d_loc4, torch.zeros_like(d_loc4)], dim=-1)
-            d_loc4 = d_loc4.contiguous()
-        if d_pi is None:
-            d_pi_c = torch.zeros(N, K, device=dev, dtype=torch.float32)
-        else:
-            if tuple(d_pi.shape) != (N, K):
-                raise _lib.TrajsdeError(f"d_pi must be [{N},{K}], got {tuple(d_pi.shape)}")
-            d_pi_c = d_pi.detach().to(device=dev, dtype=torch.float32).contiguous()
+        d_loc4, d_pi_c = self._cotangents(d_loc, d_pi, K, N, T, dev, allow_two_channels=True)
         L = _lib.lib()
         stage = _lib.STAGE_DECODER_COT_BWD
-        names = self.param_names(stage)
-        grads = self._grad_buffers(stage)
-        arr, _keep = grads.pointer_array()
-        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
-        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
+        names, grads, arr, d_local, d_global = self._backward_outputs(stage, N, K, dev)
         cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
-        ws_bytes = L.trajsde_decoder_cotangent_backward_ws_bytes(N, K, T, sched.n_euler)
-        if ws_bytes < 0:
-            raise _lib.TrajsdeError(f"trajsde_decoder_cotangent_backward_ws_bytes: {L.trajsde_last_error().decode()}")
+        ws_bytes = self._checked_ws_bytes("trajsde_decoder_cotangent_backward_ws_bytes", N, K, T, sched.n_euler)
         with torch.cuda.device(dev):
             ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
             _lib.check(L.trajsde_decoder_cotangent_backward(
@@ -1148,20 +1171,12 @@ class StageRuntime:
                                     "(dec_hivt_nusargo_grid.py:31, losses/laplace_nll_loss.py:28 chunks loc | scale out of four channels)")
         dev = local_embed.device
         K, T, N = int(m.num_modes), int(m.future_steps), local_embed.shape[0]
-        y = data["y"]
-        if y is None or tuple(y.shape) != (N, T, 2):
-            raise _lib.TrajsdeError(f"data['y'] must be [{N},{T},2] (rotated targets)")
-        y = y.to(torch.float32).contiguous()
-        mask = out["reg_mask"].contiguous().view(torch.uint8)
+        y, mask = self._targets_and_mask(data, out, N, T, "rotated targets")
         L = _lib.lib()
         stage = _lib.STAGE_DECODER_MLP_BWD if nll_eps is None else _lib.STAGE_DECODER_MLP_NLL_BWD
-        names = self.param_names(stage)
-        grads = self._grad_buffers(stage)
-        arr, _keep = grads.pointer_array()
+        names, grads, arr, d_local, d_global = self._backward_outputs(stage, N, K, dev)
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         best = torch.empty(N, device=dev, dtype=torch.int32)
-        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
-        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             head = (N, K, T, self.blob(stage).data_ptr(), local_embed.contiguous().data_ptr(), global_embed.contiguous().data_ptr(),
                     _loc4(out).data_ptr(), y.data_ptr(), mask.data_ptr())
@@ -1196,29 +1211,14 @@ class StageRuntime:
         loc4 = _loc4(out)
         if tuple(loc4.shape) != (K, N, T, 4):
             raise _lib.TrajsdeError(f"out['loc'] must be [{K},{N},{T},4], got {tuple(loc4.shape)}")
+        # (the one decoder backward that checks and casts the embeddings, a guard for callers that bring their own; the other three
+        #  hand them to the kernels as given, float32 [N,64] and [K,N,64] as the stage forwards make them)
         local_c, global_c = local_embed.to(torch.float32).contiguous(), global_embed.to(torch.float32).contiguous()
-        if d_loc is None:
-            d_loc4 = torch.zeros(K, N, T, 4, device=dev, dtype=torch.float32)
-        else:
-            if tuple(d_loc.shape) != (K, N, T, 4):
-                raise _lib.TrajsdeError(f"d_loc must be [{K},{N},{T},4], got {tuple(d_loc.shape)}")
-            d_loc4 = d_loc.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if d_pi is None:
-            d_pi_c = torch.zeros(N, K, device=dev, dtype=torch.float32)
-        else:
-            if tuple(d_pi.shape) != (N, K):
-                raise _lib.TrajsdeError(f"d_pi must be [{N},{K}], got {tuple(d_pi.shape)}")
-            d_pi_c = d_pi.detach().to(device=dev, dtype=torch.float32).contiguous()
+        d_loc4, d_pi_c = self._cotangents(d_loc, d_pi, K, N, T, dev, allow_two_channels=False)
         L = _lib.lib()
         stage = _lib.STAGE_DECODER_MLP_COT_BWD
-        names = self.param_names(stage)
-        grads = self._grad_buffers(stage)
-        arr, _keep = grads.pointer_array()
-        d_local = torch.empty(N, D, device=dev, dtype=torch.float32)
-        d_global = torch.empty(K, N, D, device=dev, dtype=torch.float32)
-        ws_bytes = L.trajsde_mlp_decoder_cotangent_backward_ws_bytes(N, K, T)
-        if ws_bytes < 0:
-            raise _lib.TrajsdeError(f"trajsde_mlp_decoder_cotangent_backward_ws_bytes: {L.trajsde_last_error().decode()}")
+        names, grads, arr, d_local, d_global = self._backward_outputs(stage, N, K, dev)
+        ws_bytes = self._checked_ws_bytes("trajsde_mlp_decoder_cotangent_backward_ws_bytes", N, K, T)
         with torch.cuda.device(dev):
             ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
             _lib.check(L.trajsde_mlp_decoder_cotangent_backward(
