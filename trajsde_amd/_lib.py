@@ -164,6 +164,14 @@ EXT_SIGNATURES = {
                                                      C.POINTER(P), C.c_int, P, P, P]),
 }
 
+# include/trajsde_hip_cotangent_sel.h: the same backward over each actor's supported mode only (csrc/decoder_cot_sel_bwd.hip); the dense
+# entry point's arguments plus the two status words.  A table of its own, as below
+COT_SEL_EXT_SIGNATURES = {
+    "trajsde_decoder_cotangent_backward_sel_ws_bytes": (I64, [I32, C.c_int, C.c_int, C.c_int]),
+    "trajsde_decoder_cotangent_backward_sel": (C.c_int, [I32, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, C.POINTER(Noise), P, F32, P, P, P, I64,
+                                                         C.POINTER(P), C.c_int, P, P, P, P]),
+}
+
 # include/trajsde_hip_grid_cotangent.h: the vanilla HiVT variant's extension header (a table of its own: the two above are each pinned,
 # name by name, by the tests of the header they mirror)
 GRID_EXT_SIGNATURES = {
@@ -193,7 +201,7 @@ def lib() -> C.CDLL:
         # ends up with two HIP runtimes and ours reports "no ROCm-capable device".
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **COT_SEL_EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

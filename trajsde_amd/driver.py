@@ -759,8 +759,10 @@ def train(model, batches_per_epoch, epochs: int, seed: int = 0, log=None, ckpt_p
 
     def settle(pending):
         if pending is not None:
-            loss_t, epoch_, i_, parts, norm_t = pending
+            loss_t, epoch_, i_, parts, norm_t, support_t = pending
             history.append(float(loss_t))
+            if support_t is not None:                         # `cotangent_support: winner`: that step's two status words, written
+                model.check_cotangent_support(support_t)      # ahead of the loss that has just been waited for
             if norm_t is not None:                            # the step's gradient norm before clipping: on the device until here, where
                 parts["grad_norm"] = float(norm_t[0])         # the loss has just been waited for
             if log:
@@ -778,7 +780,8 @@ def train(model, batches_per_epoch, epochs: int, seed: int = 0, log=None, ckpt_p
             loss.backward()
             flat.all_reduce_mean()
             flat.step()
-            mine = (loss.detach(), epoch, i, dict(getattr(model, "last_losses", None) or {}), flat.last_grad_norm)
+            mine = (loss.detach(), epoch, i, dict(getattr(model, "last_losses", None) or {}), flat.last_grad_norm,
+                    getattr(model, "last_support_status", None))
             step += 1
             batch = fetch(it, step)
             settle(pending)
@@ -866,6 +869,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gradient-clip-val", "--gradient_clip_val", dest="gradient_clip_val", type=float, default=None, metavar="FLOAT",
                     help="--train: clip the global gradient norm to FLOAT before every optimizer step (Lightning's "
                          "Trainer(gradient_clip_val=...); 0 or absent: no clipping)")
+    ap.add_argument("--cotangent-support", "--cotangent_support", dest="cotangent_support", choices=("all", "winner"), default=None,
+                    help="--train, loss sets on the cotangent route: replay all K * N decoder paths, or only each actor's one mode "
+                         "with a non-zero dL/dloc (winner-takes-all losses on loc); absent: the YAML's cotangent_support (default all)")
     return ap
 
 
@@ -898,6 +904,8 @@ def main() -> None:
     model = build_model(cfg, args.ckpt, dev, init_seed=0 if args.ckpt is None else None)
     if args.train:
         model.gradient_clip_val = args.gradient_clip_val
+        if args.cotangent_support is not None:
+            model.cotangent_support = args.cotangent_support
         if args.data:
             per_epoch = datamodule_train_batches(cfg, dev, rank, world, args.nu_dir, args.argo_dir)
         else:

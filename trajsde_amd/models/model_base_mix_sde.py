@@ -78,6 +78,12 @@ class _PathLoss(torch.autograd.Function):
 
 
 class PredictionModelSDENet(GlueBase):
+    # `cotangent_support` (model_specific.kwargs): what the cotangent route replays.  "all": every one of the K * N paths.  "winner": only
+    # the one mode per actor in which dL/dloc is non-zero -- for loss sets whose losses on `loc` are winner-takes-all, e.g.
+    # [L2, DiffBCE, SoftTargetCrossEntropyLoss]; check_cotangent_support() tells when a step broke that premise.  The welded sets ignore it.
+    cotangent_support = "all"
+    last_support_status = None
+
     def forward(self, data, noise: Optional["runtime.NoiseSpec"] = None, preserve_side_effects: Optional[bool] = None):
         """MODEL:74-102.  `noise` (optional, ours) selects the Philox seed or injected normals; the default
         draws a fresh Philox seed from torch's global generator, like the reference draws fresh noise.
@@ -117,6 +123,19 @@ class PredictionModelSDENet(GlueBase):
         synchronises the current stream -- call it where the host waits anyway (epoch end, when a loss is read)"""
         from trajsde_amd import _lib
         _lib.check_range()
+
+    def check_cotangent_support(self, status: Optional[torch.Tensor] = None) -> None:
+        """`cotangent_support: winner` only: raise if the cotangent route's last step (or the step whose "support_status" tensor is
+        handed in) met an actor whose dL/dloc was non-zero in more than one mode -- its gradients then covered the lowest such mode
+        alone.  Reads two words off the device, so it synchronises: call it where the host waits anyway, like check_range()."""
+        from trajsde_amd import _lib
+        status = self.last_support_status if status is None else status
+        if status is None:
+            return
+        many, some = (int(v) for v in status.tolist())
+        if many:
+            raise _lib.TrajsdeError(f"cotangent_support: winner -- dL/dloc of {many} actor(s) (of {some} with any) is non-zero in more "
+                                    "than one mode: the loss set is not winner-takes-all on `loc`; train it with cotangent_support: all")
 
     def _cotangent_route(self) -> bool:
         """True when the configured loss set is not one the fused backward entry points differentiate ({L2 | LaplaceNLLLoss}
@@ -183,7 +202,8 @@ class PredictionModelSDENet(GlueBase):
         out, local, glob, enc_tape, agg_tape = self._forward_stages(data, noise, keep_tapes=True)
         if custom:
             values, total, d_loc, d_pi = self._torch_losses(data, out, skip=("DiffBCE",))
-            dec = dec_rt.decoder_cotangent_backward(data, local, glob, out, noise, d_loc, d_pi)
+            dec = dec_rt.decoder_cotangent_backward(data, local, glob, out, noise, d_loc, d_pi, support=self.cotangent_support)
+            self.last_support_status = dec.get("support_status")
             w_dec = 1.0                                       # (the loss weights are inside dL/dloc and dL/dpi)
         else:
             reg, eps = self._regression_loss()
@@ -260,9 +280,11 @@ class PredictionModelSDENet(GlueBase):
         backward.  Any other loss set -- further `loss(data, output)` callables on `loc` / `pi`, or L2 together with LaplaceNLLLoss --
         takes the cotangent route: the losses (DiffBCE apart) are evaluated by torch on the forward's `loc` and `pi`, and their
         gradients dL/dloc, dL/dpi go through the HIP backward of all K modes (trajsde_decoder_cotangent_backward), which trains the
-        `pi` and `scale` heads as well.  A decoder with `method: milstein` trains under the fused sets (its reverse sweep differentiates
+        `pi` and `scale` heads as well -- or, with `cotangent_support: winner`, of each actor's one supported mode (and `pi` over all K).  A decoder with `method: milstein` trains under the fused sets (its reverse sweep differentiates
         the gdg term: trajsde_decoder_*_backward_milstein), on the GPU only; the cotangent route is Euler-only."""
         custom = self._cotangent_route()
+        if custom and self.cotangent_support not in ("all", "winner"):
+            raise ValueError(f"cotangent_support {self.cotangent_support!r}: 'all' or 'winner'")
         if custom and getattr(self.decoder, "method", "euler") == "milstein":
             raise NotImplementedError("`method: milstein` trains under L2 or LaplaceNLLLoss (+ DiffBCE) only: the cotangent route that "
                                       f"differentiates {self.loss_names} is built for the Euler-Maruyama solve")

@@ -760,12 +760,21 @@ class StageRuntime:
         return {"loss": loss[0], "best_mode": best, "grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
 
     def decoder_cotangent_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
-                                   noise: NoiseSpec, d_loc: Optional[torch.Tensor], d_pi: Optional[torch.Tensor]) -> Dict[str, object]:
+                                   noise: NoiseSpec, d_loc: Optional[torch.Tensor], d_pi: Optional[torch.Tensor],
+                                   support: str = "all") -> Dict[str, object]:
         """Vector-Jacobian product of the decoder stage (DEC:77-105, Euler-Maruyama) at the forward's noise, from caller-supplied
         cotangents: `d_loc` = dL/dloc [K,N,T,4] (or [K,N,T,2] without the scale head) and `d_pi` = dL/dpi [N,K] of ANY loss over all K
         modes; None is zeros.  `out` = decoder_forward(...), `noise` the NoiseSpec it ran with.  Every one of the K * N paths is
         replayed and swept in reverse, so the workspace is about K times decoder_l2_backward's.  Returns {"grads": {param name:
-        tensor} keyed by param_names(STAGE_DECODER_COT_BWD) -- `scale.*` and `pi.*` included --, "d_local_embed", "d_global_embed"}."""
+        tensor} keyed by param_names(STAGE_DECODER_COT_BWD) -- `scale.*` and `pi.*` included --, "d_local_embed", "d_global_embed"}.
+        `support="winner"` (trajsde_decoder_cotangent_backward_sel) is for a `d_loc` that is non-zero in at most one mode per actor, as a
+        winner-takes-all regression loss leaves it: that mode is found on the device and only its path is replayed and swept, so the
+        SDE tape is decoder_nll_backward's whatever K is; `pi` is differentiated over all K modes as before.  The result then also holds
+        "support_status", a device tensor of two int32 (actors with more than one supported mode -- the premise is violated unless this is
+        0, and the gradients are then those of each actor's lowest supported mode alone --, actors with any support) and
+        "support_mode" [N] int32, the selected modes; no host synchronisation is added, reading them is the caller's."""
+        if support not in ("all", "winner"):
+            raise ValueError(f"support {support!r}: 'all' (every one of the K * N paths) or 'winner' (each actor's one supported mode)")
         m = self.module
         if getattr(m, "method", "euler") == "milstein":
             raise NotImplementedError("decoder_cotangent_backward differentiates the Euler-Maruyama solve only: `method: milstein` trains "
@@ -783,15 +792,22 @@ class StageRuntime:
         stage = _lib.STAGE_DECODER_COT_BWD
         names, grads, arr, d_local, d_global = self._backward_outputs(stage, N, K, dev)
         cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
-        ws_bytes = self._checked_ws_bytes("trajsde_decoder_cotangent_backward_ws_bytes", N, K, T, sched.n_euler)
+        name = "trajsde_decoder_cotangent_backward" + ("_sel" if support == "winner" else "")
+        ws_bytes = self._checked_ws_bytes(name + "_ws_bytes", N, K, T, sched.n_euler)
+        res = {"grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
         with torch.cuda.device(dev):
             ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-            _lib.check(L.trajsde_decoder_cotangent_backward(
+            tail = (_stream(),)
+            if support == "winner":
+                res["support_status"] = torch.empty(2, device=dev, dtype=torch.int32)
+                res["support_mode"] = ws[:4 * N].view(torch.int32)          # (the selection: the workspace's first N words)
+                tail = (res["support_status"].data_ptr(), _stream())
+            _lib.check(getattr(L, name)(
                 N, K, T, self.blob().data_ptr(), self.blob(stage).data_ptr(), local_embed.contiguous().data_ptr(),
                 global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler, out_tab.data_ptr(), C.byref(cn),
                 loc4.data_ptr(), float(m.min_scale), d_loc4.data_ptr(), d_pi_c.data_ptr(), ws.data_ptr(), ws_bytes, arr, len(names),
-                d_local.data_ptr(), d_global.data_ptr(), _stream()), "trajsde_decoder_cotangent_backward")
-        return {"grads": grads, "d_local_embed": d_local, "d_global_embed": d_global}
+                d_local.data_ptr(), d_global.data_ptr(), *tail), name)
+        return res
 
     # ---------------------------------------------------------------- encoder
     def encoder_forward(self, data, noise: Optional[NoiseSpec] = None, preserve_side_effects: bool = False):
