@@ -185,6 +185,12 @@ CLIP_EXT_SIGNATURES = {
     "trajsde_grad_norm_clip": (C.c_int, [P, I64, F32, P, I64, P, P]),
     "trajsde_adamw_step_clipped": (C.c_int, [P, P, P, P, I64, F32, F32, F32, F32, F32, C.c_int, F32, F32, P, P]),
 }
+# include/trajsde_hip_encoder_cotangent.h: the encoder backward from the cotangents of local_embed, diff_in and diff_out
+# (csrc/encoder_cot_bwd.hip): trajsde_encoder_backward's arguments with `diff_weight`, `diff_loss` replaced by the two cotangent pointers
+ENC_COT_EXT_SIGNATURES = {
+    "trajsde_encoder_cotangent_backward": (C.c_int, [C.POINTER(Batch), C.POINTER(Graph), P, P, P, P, P, C.POINTER(Noise), P, P, P, P, I64,
+                                                     C.POINTER(P), C.c_int, P, P, C.POINTER(Dropout), C.c_int, P, I64, P]),
+}
 # the reduction's geometry (csrc/clip.hip; the workspace query returns 8 bytes per workgroup, which ties these to the library):
 # a workgroup takes CLIP_WG_FLOATS consecutive elements a pass, the grid is at most CLIP_MAX_WGS workgroups and strides beyond that
 CLIP_WG_FLOATS, CLIP_MAX_WGS = 2048, 512
@@ -201,7 +207,8 @@ def lib() -> C.CDLL:
         # ends up with two HIP runtimes and ours reports "no ROCm-capable device".
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **COT_SEL_EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **COT_SEL_EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES,
+                                   **ENC_COT_EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

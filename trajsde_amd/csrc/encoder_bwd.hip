@@ -17,6 +17,7 @@
 #include "attn_common.hpp"
 #include "bwd.hpp"
 #include "common.hpp"
+#include "encoder_bwd_host.hpp"
 #include "kernels.hpp"
 #include "layouts.hpp"
 #include "philox.hpp"
@@ -951,31 +952,36 @@ int trajsde_encoder_forward_train(const trajsde_batch* b, const trajsde_graph* g
   return TRAJSDE_OK;
 }
 
-int trajsde_encoder_backward(const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob_fwd,
-                             const float* blob_bwd, const float* step_tab /*HOST [H,8]*/, const float* step_tab_dev,
-                             const trajsde_noise* noise, const float* d_local, float diff_weight, void* ws, int64_t ws_bytes,
-                             float* diff_loss, float* const* grads, int n_grads, float* d_latent, float* d_aa_out,
-                             const trajsde_dropout* dropout, int tape_valid, void* scratch, int64_t scratch_bytes, void* stream_) {
-  TS_REQUIRE(b && g && rot && blob_fwd && blob_bwd && step_tab && step_tab_dev && d_local && ws && diff_loss && grads,
-             "encoder_backward: null pointer");
-  TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), "encoder_backward: dropout p must be in [0, 1)");
-  TS_REQUIRE(!state_bf16(), "encoder_backward: the backward pass keeps its tape in fp32; switch trajsde_state_storage(0) for training");
+}  // extern "C"
+
+// The encoder backward behind its DLDG producer: what trajsde_encoder_backward (DiffBCE welded in: k_diffbce) and
+// trajsde_encoder_cotangent_backward (caller-supplied cotangents of diff_in / diff_out: encoder_cot_bwd.hip k_diff_cot) share.  `dldg`
+// is enqueued where k_diffbce always was -- behind the ALEncoder chain, in front of the recurrence sweep -- and `who` names the
+// entry point in the refusals.
+int tsde::encoder_backward_run(const char* who_, const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob_fwd,
+                               const float* blob_bwd, const float* step_tab /*HOST [H,8]*/, const float* step_tab_dev,
+                               const trajsde_noise* noise, const float* d_local, void* ws, int64_t ws_bytes, float* const* grads, int n_grads,
+                               float* d_latent, float* d_aa_out, const trajsde_dropout* dropout, int tape_valid, void* scratch,
+                               int64_t scratch_bytes, void* stream_, const DldgProducer& dldg) {
+  const std::string who = who_;
+  TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), who + ": dropout p must be in [0, 1)");
+  TS_REQUIRE(!state_bf16(), who + ": the backward pass keeps its tape in fp32; switch trajsde_state_storage(0) for training");
   const DropArg drop_aa = dropout ? make_drop(dropout->p, dropout->seed, 0) : no_drop();     // block ids of dropout.hpp
   const DropArg drop_al = dropout ? make_drop(dropout->p, dropout->seed, 1) : no_drop();
-  TS_REQUIRE(g->aa_dst && g->la_dst && g->orig, "encoder_backward: graph not compacted (call trajsde_graph_compact)");
-  TS_REQUIRE(g->exact, "encoder_backward: needs exact list lengths (trajsde_graph_prepare, not _async)");
-  TS_REQUIRE(b->A > 0 && g->Nt == b->N + b->A, "encoder_backward: graph was prepared without the fake-agent rows");
+  TS_REQUIRE(g->aa_dst && g->la_dst && g->orig, who + ": graph not compacted (call trajsde_graph_compact)");
+  TS_REQUIRE(g->exact, who + ": needs exact list lengths (trajsde_graph_prepare, not _async)");
+  TS_REQUIRE(b->A > 0 && g->Nt == b->N + b->A, who + ": graph was prepared without the fake-agent rows");
   const std::vector<std::string> names = stage_param_names(TRAJSDE_STAGE_ENCODER_BWD, 0, 0);
-  TS_REQUIRE(n_grads == int(names.size()), "encoder_backward: gradient count does not match trajsde_param_count(ENCODER_BWD)");
+  TS_REQUIRE(n_grads == int(names.size()), who + ": gradient count does not match trajsde_param_count(ENCODER_BWD)");
   GradTable G;
   for (int i = 0; i < n_grads; ++i) {
-    TS_REQUIRE(grads[i] != nullptr, "encoder_backward: null gradient buffer " + names[i]);
+    TS_REQUIRE(grads[i] != nullptr, who + ": null gradient buffer " + names[i]);
     G.slot[names[i]] = grads[i];
   }
   EncBwdWs w(b, g, ws, ws_bytes, scratch, scratch_bytes);
-  if (!w.ok) return fail(TRAJSDE_ERR_WORKSPACE, "encoder_backward: workspace too small");
+  if (!w.ok) return fail(TRAJSDE_ERR_WORKSPACE, who + ": workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  const int N = b->N, Nt = g->Nt, H = b->H, A = b->A;
+  const int N = b->N, Nt = g->Nt, H = b->H;
   const int64_t R = int64_t(H) * Nt, Ela = g->E_la;
   const int64_t rtiles = (int64_t(Nt) + 15) / 16;
   NoiseArg na{0, nullptr, nullptr};
@@ -998,9 +1004,8 @@ int trajsde_encoder_backward(const trajsde_batch* b, const trajsde_graph* g, con
     if (int rc = run_attn_chain(c, d_local, w, wc, G, w.DLAT, st)) return rc;
     if (d_latent) TS_HIP(hipMemcpyAsync(d_latent, w.DLAT, size_t(N) * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  // ---- DiffBCE on the picked diffusion values
-  TS_LAUNCH(k_diffbce, 1, 1024, 0, st, w.GS, g->eos_idx, g->pick_slot, Nt, A, diff_weight, w.DLDG, w.scal);
-  TS_HIP(hipMemcpyAsync(diff_loss, w.scal, sizeof(float), hipMemcpyDeviceToDevice, st));
+  // ---- DLDG: d L / d (picked diffusion value) per row -- DiffBCE, or the caller's cotangents
+  if (int rc = dldg(w.GS, w.DLDG, w.scal, st)) return rc;
   // ---- recurrence, last iteration first
   {
     RecurTab tab;
@@ -1094,6 +1099,25 @@ int trajsde_encoder_backward(const trajsde_batch* b, const trajsde_graph* g, con
   if (d_aa_out) TS_HIP(hipMemcpyAsync(d_aa_out, w.DAA, size_t(R) * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (int rc = aa_encoder_backward(b, g, rot, blob_fwd, blob_bwd, w, wc, G, 8, st, drop_aa)) return rc;
   return sums.finish();
+}
+
+extern "C" {
+
+int trajsde_encoder_backward(const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob_fwd,
+                             const float* blob_bwd, const float* step_tab /*HOST [H,8]*/, const float* step_tab_dev,
+                             const trajsde_noise* noise, const float* d_local, float diff_weight, void* ws, int64_t ws_bytes,
+                             float* diff_loss, float* const* grads, int n_grads, float* d_latent, float* d_aa_out,
+                             const trajsde_dropout* dropout, int tape_valid, void* scratch, int64_t scratch_bytes, void* stream_) {
+  TS_REQUIRE(b && g && rot && blob_fwd && blob_bwd && step_tab && step_tab_dev && d_local && ws && diff_loss && grads,
+             "encoder_backward: null pointer");
+  // DiffBCE on the picked diffusion values
+  const DldgProducer bce = [&](const float* GS, float* DLDG, float* scal, hipStream_t st) -> int {
+    TS_LAUNCH(k_diffbce, 1, 1024, 0, st, GS, g->eos_idx, g->pick_slot, g->Nt, b->A, diff_weight, DLDG, scal);
+    TS_HIP(hipMemcpyAsync(diff_loss, scal, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return TRAJSDE_OK;
+  };
+  return encoder_backward_run("encoder_backward", b, g, rot, blob_fwd, blob_bwd, step_tab, step_tab_dev, noise, d_local, ws, ws_bytes, grads,
+                              n_grads, d_latent, d_aa_out, dropout, tape_valid, scratch, scratch_bytes, stream_, bce);
 }
 
 // ------------------------------------------------------------------ vanilla LocalEncoder backward (GENC:52-93)

@@ -5,7 +5,7 @@ Constructor kwargs as in configs/nusargo/hivt_nuSArgo_sdesepenc_sdedec.yml:51-59
 `aggregator(data=data, local_embed=...) -> [K, N, 64]`; state_dict keys as in SURVEY.md App. C.
 """
 from trajsde_amd.models.params import ParamTree
-from trajsde_amd import runtime
+from trajsde_amd import runtime, stage_autograd
 
 
 class GlobalInteractor(ParamTree):
@@ -30,5 +30,9 @@ class GlobalInteractor(ParamTree):
 
     def forward(self, data, local_embed, noise=None, prepared=None):
         """`noise` (ours, optional): the NoiseSpec whose dropout key seeds this stage's train-mode dropout masks;
-        `prepared` (ours, optional): the handle of `runtime.StageRuntime.prefetch_rel_embed` of this forward"""
+        `prepared` (ours, optional): the handle of `runtime.StageRuntime.prefetch_rel_embed` of this forward.
+        With `autograd: true` among the kwargs, and `local_embed` or a parameter requiring grad while grad mode is on, the output
+        comes from the stage's autograd node (stage_autograd.AggregatorNode)"""
+        if stage_autograd.active(self, local_embed):
+            return stage_autograd.aggregator(self, data, local_embed, noise, prepared=prepared)
         return self._rt.aggregator_forward(data, local_embed, noise, prepared=prepared)

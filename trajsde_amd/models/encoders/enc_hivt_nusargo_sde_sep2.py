@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from trajsde_amd.models.params import ParamTree
-from trajsde_amd import runtime
+from trajsde_amd import runtime, stage_autograd
 from trajsde_amd.schedule import SDE_METHODS
 
 
@@ -56,9 +56,13 @@ class LocalEncoderSDESepPara2(ParamTree):
 
     def forward(self, data, noise: Optional["runtime.NoiseSpec"] = None, preserve_side_effects: Optional[bool] = None):
         """`preserve_side_effects` (default: the `preserve_side_effects` constructor kwarg, else False): also leave
-        `data['edge_index_{t}']` / `data['edge_attr_{t}']` on the batch as the reference's forward does (ENC:107-110)."""
+        `data['edge_index_{t}']` / `data['edge_attr_{t}']` on the batch as the reference's forward does (ENC:107-110).
+        With `autograd: true` among the kwargs, and a parameter that requires grad while grad mode is on, the outputs come from the
+        stage's autograd node (stage_autograd.EncoderNode): `local_embed`, `diff_in`, `diff_out` carry a `grad_fn`."""
         if preserve_side_effects is None:
             preserve_side_effects = bool(getattr(self, "preserve_side_effects", False))
+        if stage_autograd.active(self):
+            return stage_autograd.encoder(self, data, noise, preserve_side_effects=preserve_side_effects)
         return self._rt.encoder_forward(data, noise, preserve_side_effects=preserve_side_effects)
 
     def forward_ood(self, data, noise: Optional["runtime.NoiseSpec"] = None):

@@ -885,15 +885,44 @@ class StageRuntime:
         (+ "d_latent" [N,64], "d_aa_out" [H,Nt,64] with want_boundaries).  `tape`: what encoder_forward_train returned for
         this very step; without it the forward is recomputed inside.  `keep_scratch` (reproducibility checks): the backward's
         scratch buffer starts zeroed and is returned as "_scratch"."""
+        return self._encoder_backward(data, d_local, noise, want_boundaries, tape, keep_scratch, diff_weight=diff_weight)
+
+    def encoder_cotangent_backward(self, data, d_local: Optional[torch.Tensor], d_diff_in: Optional[torch.Tensor],
+                                   d_diff_out: Optional[torch.Tensor], noise: NoiseSpec, tape=None,
+                                   want_boundaries: bool = False) -> Dict[str, object]:
+        """Vector-Jacobian product of LocalEncoderSDESepPara2.forward at the forward's noise, from caller-supplied cotangents of its
+        three differentiable outputs (trajsde_encoder_cotangent_backward): `d_local` = dL/d local_embed [N,64], `d_diff_in` /
+        `d_diff_out` = dL/d diff_in, dL/d diff_out [A,64]; None is zeros.  No loss is formed inside.  Returns {"grads": {param name:
+        tensor}} keyed by param_names(STAGE_ENCODER_BWD) (+ "d_latent", "d_aa_out" with want_boundaries); `tape` as in
+        encoder_backward."""
+        return self._encoder_backward(data, d_local, noise, want_boundaries, tape, False, cotangents=(d_diff_in, d_diff_out))
+
+    def _encoder_backward(self, data, d_local: Optional[torch.Tensor], noise: NoiseSpec, want_boundaries: bool, tape, keep_scratch: bool,
+                          diff_weight: Optional[float] = None, cotangents=None) -> Dict[str, object]:
+        """shared body of encoder_backward (`diff_weight`: DiffBCE welded in) and encoder_cotangent_backward (`cotangents`: dL/d diff_in,
+        dL/d diff_out): gradient buffers, tape, the scratch allocated late"""
         m = self.module
+        what = "encoder_backward" if cotangents is None else "encoder_cotangent_backward"
         if noise is None:
-            raise _lib.TrajsdeError("encoder_backward needs the NoiseSpec of the forward pass")
+            raise _lib.TrajsdeError(f"{what} needs the NoiseSpec of the forward pass")
         gc = GraphContext.get(data, float(m.local_radius), int(m.historical_steps), noise)
         dev = gc.device
         L = _lib.lib()
-        H, N, Nt = gc.batch.H, gc.batch.N, gc.graph.Nt
+        H, N, A, Nt = gc.batch.H, gc.batch.N, gc.batch.A, gc.graph.Nt
+        if d_local is None and cotangents is not None:
+            d_local = torch.zeros(N, D, device=dev, dtype=torch.float32)
         if tuple(d_local.shape) != (N, D):
             raise _lib.TrajsdeError(f"d_local must be [{N},{D}]")
+        if cotangents is not None:
+            _require_gpu(d_local, "d_local")
+            cots = []
+            for name, t in zip(("d_diff_in", "d_diff_out"), cotangents):
+                if t is not None:
+                    if tuple(t.shape) != (A, D):
+                        raise _lib.TrajsdeError(f"{name} must be [{A},{D}], got {tuple(t.shape)}")
+                    _require_gpu(t, name)
+                    t = t.detach().to(torch.float32).contiguous()
+                cots.append(t)
         tab = self._enc_table()
         tab_dev = _TABLES_DEV.get((id(tab), str(dev)))                     # (not setdefault: its default would be built -- a blocking
         if tab_dev is None:                                                #  pageable host-to-device copy -- on every call)
@@ -901,7 +930,7 @@ class StageRuntime:
         names = self.param_names(_lib.STAGE_ENCODER_BWD)
         grads = self._grad_buffers(_lib.STAGE_ENCODER_BWD)
         arr, _keep = grads.pointer_array()
-        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if cotangents is None else None
         d_lat = torch.empty(N, D, device=dev, dtype=torch.float32) if want_boundaries else None
         d_aa = torch.empty(H, Nt, D, device=dev, dtype=torch.float32) if want_boundaries else None
         if tape is not None:
@@ -915,15 +944,22 @@ class StageRuntime:
         scratch = (torch.zeros if keep_scratch else torch.empty)(sc_bytes, device=dev, dtype=torch.uint8)
         cn = noise.c_noise(noise.z_enc, noise.enc_row_ids)
         dr = noise.c_dropout(m)                                            # the forward's masks, regenerated from the same key
-        with torch.cuda.device(dev):
-            _lib.check(L.trajsde_encoder_backward(
-                C.byref(gc.batch), C.byref(gc.graph), gc.rot.data_ptr(), self.blob().data_ptr(),
+        d_local_c = d_local.to(torch.float32).contiguous()
+        head = (C.byref(gc.batch), C.byref(gc.graph), gc.rot.data_ptr(), self.blob().data_ptr(),
                 self.blob(_lib.STAGE_ENCODER_BWD).data_ptr(), tab.ctypes.data_as(C.c_void_p), tab_dev.data_ptr(), C.byref(cn),
-                d_local.to(torch.float32).contiguous().data_ptr(), float(diff_weight), ws.data_ptr(), ws_bytes, loss.data_ptr(),
-                arr, len(names), _ptr(d_lat), _ptr(d_aa), C.byref(dr) if dr is not None else None, 1 if tape is not None else 0,
-                scratch.data_ptr(), sc_bytes, _stream()),
-                "trajsde_encoder_backward")
-        out = {"grads": grads, "diff_loss": loss[0]}
+                d_local_c.data_ptr())
+        tail = (arr, len(names), _ptr(d_lat), _ptr(d_aa), C.byref(dr) if dr is not None else None, 1 if tape is not None else 0,
+                scratch.data_ptr(), sc_bytes, _stream())
+        with torch.cuda.device(dev):
+            if cotangents is None:
+                _lib.check(L.trajsde_encoder_backward(*head, float(diff_weight), ws.data_ptr(), ws_bytes, loss.data_ptr(), *tail),
+                           "trajsde_encoder_backward")
+            else:
+                _lib.check(L.trajsde_encoder_cotangent_backward(*head, _ptr(cots[0]), _ptr(cots[1]), ws.data_ptr(), ws_bytes, *tail),
+                           "trajsde_encoder_cotangent_backward")
+        out = {"grads": grads}
+        if cotangents is None:
+            out["diff_loss"] = loss[0]
         if want_boundaries:
             out.update(d_latent=d_lat, d_aa_out=d_aa)
         if keep_scratch:
