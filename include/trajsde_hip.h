@@ -46,9 +46,16 @@ int trajsde_split_products(void);
  * reads and writes hold bf16 elements. */
 int trajsde_state_storage(int mode);
 /* fp16 range guard of the split-precision products (csrc/range.hpp).  Kernels that feed a data-dependent, unnormalised
- * tensor (SDE states, rows entering the recurrence / the decoder, attention aggregates, FFN hidden units) or a weight to an
- * fp16x3 product set a sticky per-device bit when a magnitude reaches 65504, where the fp16 pieces would saturate.  This call
- * synchronises `stream`, reads (and with reset != 0 clears) the bits and returns TRAJSDE_OK or TRAJSDE_ERR_UNSUPPORTED with
+ * tensor or a weight to an fp16x3 product set a sticky per-device bit when a magnitude reaches 65504 (+-inf included), where
+ * the fp16 pieces would saturate.  The sites, bit by bit:
+ *   0  decoder SDE state (trajsde_decoder_forward[_milstein], trajsde_sde_step, the replays of the decoder backward entry points)
+ *   1  decoder embedding inputs: local_embed / global_embed rows (both decoders' forwards and every decoder backward entry point)
+ *   2  encoder latent state          3  aa_out rows entering the GRU        (inference, out-of-distribution and training recurrences)
+ *   4  attention aggregate / gated update entering lin_ih, out_proj (AA, AL and global layers; the vanilla temporal encoder's out_proj)
+ *   5  FFN hidden units entering mlp.3 (inference and training forwards)
+ *   6  a weight without an fp16 image (checked when the weight images are packed)
+ * This call synchronises `stream`, reads (and with reset != 0 clears; reset == 0 leaves them set) the bits of every
+ * translation unit, ORed into one mask, and returns TRAJSDE_OK or TRAJSDE_ERR_UNSUPPORTED with
  * the affected sites in trajsde_last_error(); *sites_out (optional) receives the bit mask.  Call it where the host
  * synchronises anyway (end of an evaluation epoch, when a loss value is read); always 0 in a bf16x6 build. */
 int trajsde_range_status(int reset, uint32_t* sites_out, void* stream);

@@ -848,8 +848,9 @@ def test_bf16_state_storage(dev):
 
 def test_fp16_range_guard_is_loud(dev):
     """magnitudes the fp16 pieces cannot hold (>= 65504) are refused with TRAJSDE_ERR_UNSUPPORTED instead of saturating
-    silently: a hidden state of 7e4 through trajsde_sde_step, an aggregate of 7e4 through the node block of the aggregator,
-    a weight of 1e5; and the flag is sticky until it is read"""
+    silently: a hidden state of 7e4 through trajsde_sde_step, an embedding element of 1e5 through the SDE decoder, a weight of
+    1e5; and the flag is sticky until it is read.  (Every other site and route -- an aggregate of 7e4 through the node block of
+    the aggregator among them -- is in tests/test_gpu_range_guard.py.)"""
     import ctypes as C
     from trajsde_amd import _lib
     from trajsde_amd.runtime import NoiseSpec, rotate_inputs

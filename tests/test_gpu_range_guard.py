@@ -1,0 +1,1297 @@
+"""The fp16 range of the split-precision products at both ends (-m gpu).
+
+UPPER END (csrc/range.hpp).  The default build multiplies fp32 operands as two fp16 pieces; a magnitude >= 65504 has no such pieces and
+the kernels that feed an unnormalised tensor to a product must say so through trajsde_range_status.  TABLE below is site x route: every
+cell is a case that runs here, or a one-line reason why the route cannot reach the site.  A case plants a magnitude through something a
+caller controls (a plain bias, an embedding element, a matrix element: `plant`) and checks
+  over the limit   7e4 -> TRAJSDE_ERR_UNSUPPORTED, *sites_out exactly the cell's bits, the message names the site; +inf is flagged too
+  under the limit  6e4 -> mask 0, and every output of the route within 1e-4 * max(1, max|want|) of the float64 oracle (oracle/restate*.py
+                   at the planted parameters), the observed ratio printed per case ("[range-guard] ...").
+The plants are the plain ones: nothing downstream is rescaled, so a planted 6e4 meets ordinary weights and the products of order 6e3 run
+through saturated gates, residual adds and LayerNorms as they would in a model that had drifted there.  The float32 restatement of the
+oracle meets the bound on every plant by a factor of 100 or more (the one exception is handled in `attention` below), so a miss is the
+kernels'.  What the rule cannot ask for: an fp16x3 product carries an absolute error of about 3e-8 x |operand| (the low piece of an
+ordinary weight is subnormal), 2e-3 at 6e4 -- harmless against a product of 6e3, visible if that product were made to cancel to order 1.
+
+LOWER END.  Adjoints span many binades; linear_adj scales each row by a power of two, k_wgrad6 each 64-row block, the recurrence backward
+a row per iteration.  Section 3 hands the cotangent entry points cotangents of 2^-60 .. 2^40, and per-actor scales mixed inside every
+16-row tile and 64-row block, and asks for exact proportionality where the stage is row-wise and float64 autograd where it is not."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import helpers as H
+
+pytestmark = pytest.mark.gpu
+
+LIMIT = 65504.0
+OVER, UNDER = 7.0e4, 6.0e4
+REL = 1e-4                      # the path's own bound, relative to the tensor: err <= REL * max(1, max|want|)
+SEED = 19
+J, I = 7, 9                     # the planted feature / the hidden unit the WEIGHT plant isolates
+JA = 13                         # ... of the aggregator's attention plant: in about half the channels (7 among them) three global layers on
+                                # rows that all carry 6e3 x one direction lose 1e-4 in float32 itself; in 13, 40, 50, 51 they lose 5e-7
+K, T, MAX_T = 2, 5, 0.5         # synth(S=2, n=6, L=3, F=5): N = 12, A = 2 -> Nt = 14 (one ragged tile), 21 * 14 = 294 snapshot rows, K * N = 24
+UNSUPPORTED = -4
+
+# bit i of *sites_out = csrc/range.hpp RangeSite i; the words trajsde_range_status puts into the message for it
+SITES = ("DEC_STATE", "DEC_INPUT", "ENC_STATE", "ENC_INPUT", "NODE_AGG", "FFN_HIDDEN", "WEIGHT")
+BIT = {s: 1 << i for i, s in enumerate(SITES)}
+WORDS = {"DEC_STATE": "decoder SDE state", "DEC_INPUT": "decoder embedding inputs", "ENC_STATE": "encoder latent state",
+         "ENC_INPUT": "aa_out rows entering the GRU", "NODE_AGG": "attention aggregate / gated update", "FFN_HIDDEN": "FFN hidden units",
+         "WEIGHT": "a weight (no fp16 image)"}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    spy_on_library()
+    return torch.device("cuda:0")
+
+
+CALLED, RAN = set(), set()
+
+
+@pytest.fixture(autouse=True)
+def _note_test(request):
+    RAN.add(request.node.originalname or request.node.name)
+    yield
+
+
+def spy_on_library():
+    """every launching entry point notes its name in CALLED (the accounting test at the end of this module)"""
+    from trajsde_amd import _lib
+    L = _lib.lib()          # a missing/broken HIP library is a failure, not a skip
+    if getattr(L, "_range_guard_spy", False):
+        return
+
+    def wrap(name, fn):
+        def spy(*a):
+            CALLED.add(name)
+            return fn(*a)
+        return spy
+    for name in list(_lib.SIGNATURES) + list(_lib.EXT_SIGNATURES) + list(_lib.COT_SEL_EXT_SIGNATURES) + list(_lib.GRID_EXT_SIGNATURES) + \
+            list(_lib.ENC_COT_EXT_SIGNATURES):
+        if name not in ("trajsde_range_status", "trajsde_last_error"):
+            setattr(L, name, wrap(name, getattr(L, name)))
+    L._range_guard_spy = True
+
+
+def read_flags(reset=1):
+    """(status, *sites_out, message) of trajsde_range_status on torch's current stream"""
+    from trajsde_amd import _lib
+    L = _lib.lib()
+    torch.cuda.synchronize()
+    mask = C.c_uint32(0xFFFFFFFF)
+    status = L.trajsde_range_status(int(reset), C.byref(mask), torch.cuda.current_stream().cuda_stream)
+    return status, int(mask.value), (L.trajsde_last_error().decode() if status else "")
+
+
+def fp16x3():
+    from trajsde_amd import _lib
+    return _lib.lib().trajsde_split_products() == 3
+
+
+def names_of(mask):
+    return "|".join(s for s in SITES if mask & BIT[s]) or "0"
+
+
+# ----------------------------------------------------------------------------------------------------------------- models and batches
+def sde_batch():
+    from trajsde_amd.synth import synth
+    b = synth(S=2, n=6, L=3, F=T, box=50.0, seed=5)
+    assert b.num_nodes == 12 and not bool(b["padding_mask"][:, :21].any())      # (a padded step would carry a planted state over: GRU mask)
+    return b
+
+
+def sde_model(method="euler"):
+    from trajsde_amd.models.model_base_mix_sde import PredictionModelSDENet
+    cfg = H.our_cfg(K, T, MAX_T)
+    if method == "milstein":
+        cfg["decoder"]["kwargs"]["method"] = cfg["encoder"]["kwargs"]["method"] = "milstein"
+    model = PredictionModelSDENet(**cfg, init_seed=4).eval()
+    H.perturb_parameters(model, 3)                                              # biases and LayerNorm affines off 0 / 1
+    return model, cfg
+
+
+def grid_model():
+    from trajsde_amd.models.model_base_mix import PredictionModel
+    cfg = H.grid_cfg(K, T, 4, 2, dropout=0.0)
+    model = PredictionModel(**cfg, init_seed=9).eval()
+    H.perturb_parameters(model, 3)
+    return model, cfg
+
+
+# ----------------------------------------------------------------------------------------------------------------- plants
+G0 = "aggregator.global_interactor_layers.0"
+AA = "encoder.aa_encoder"
+GRU = "encoder.gru_unit"
+TR0 = "encoder.temporal_encoder.transformer_encoder.layers.0"
+
+
+def _schedules(cfg):
+    import restate
+    from trajsde_amd.schedule import decoder_schedule, encoder_schedule
+    c = restate.flat_cfg(cfg)
+    return (encoder_schedule(c["historical_steps"], c["max_past_t"], c["minimum_step"]),
+            decoder_schedule(c["future_steps"], c["max_fut_t"], c["min_stepsize"]))
+
+
+def plant(model, cfg, name, v):
+    """write magnitude `v` where `name` says, in place (the parameters' version counters move: the next call re-packs)"""
+    p = dict(model.named_parameters())
+    with torch.no_grad():
+        def attention(pre, v_bias, j=J):
+            """agg[:, J] = v wherever a target has an edge: the value bias rides the softmax.  The gate of channel J is shut (bias -1e4),
+            so the gated update hands agg[:, J] on as it is and out_proj multiplies it too; left to chance, (1 - gate) * 6e4 with a gate
+            near 1 amplifies the gate's own float32 rounding to 4e-3."""
+            p[v_bias][j] = v
+            p[pre + ".lin_ih.bias"][j] = -1.0e4
+
+        def ffn(pre, l1=".mlp.0", l2=".mlp.3"):           # relu(.. + v) = v in hidden unit J
+            p[pre + l1 + ".bias"][J] = v
+
+        def weight(pre, l1=".mlp.0", l2=".mlp.3"):
+            """hidden unit I is the constant 2^-13 and its column of the second matrix holds v in row J: the product is of order 7.  (A
+            power of two has an exact fp16 image; 1e-4 has a 22-bit one only down to 3e-8 absolute -- its low piece is subnormal --, which
+            times 6e4 is 2e-3: the low end of the OTHER operand, not what a weight near the limit is about.)"""
+            p[pre + l1 + ".weight"][I, :] = 0.0
+            p[pre + l1 + ".bias"][I] = 2.0 ** -13
+            p[pre + l2 + ".weight"][J, I] = v
+        if name == "enc_node_agg":
+            attention(AA, AA + ".lin_v.bias")
+        elif name == "agg_node_agg":
+            attention(G0, G0 + ".lin_v_node.bias", JA)
+        elif name == "enc_ffn":
+            ffn(AA)
+        elif name == "agg_ffn":
+            ffn(G0)
+        elif name == "enc_input":                         # aa_out[:, :, J] = v + O(1), into the three nets of the GRU
+            p[AA + ".mlp.3.bias"][J] = v
+        elif name == "enc_state":                         # h_ode[:, J] = h + f dt = v at the longest step; the GRU forgets it (u[J] = sigmoid(-40))
+            es, _ = _schedules(cfg)
+            p["encoder.lsde_func.f_func.net.4.bias"][J] = v / float(np.max(es.dt))
+            p[GRU + ".update_gate.2.bias"][J] = -40.0
+        elif name == "dec_state":                         # y[:, J] grows by v / n_euler a step and reaches v with the last one
+            _, ds = _schedules(cfg)
+            p["decoder.lsde_func.f_func.net.4.bias"][J] = v / float(np.sum(ds.dt.astype(np.float64)))
+        elif name == "dec_input":                         # global_embed[1, :, J] = v; a LayerNorm follows both products that read it
+            p["aggregator.multihead_proj.bias"][64 + J] = v
+        elif name == "agg_weight":
+            weight(G0)
+        elif name == "grid_tr_agg":                       # the temporal attention's value bias: o[:, J] = v into out_proj (grid.hip k_tr_outproj)
+            p[TR0 + ".self_attn.in_proj_bias"][128 + J] = v
+        elif name == "grid_tr_ffn":
+            ffn(TR0, ".linear1", ".linear2")
+        elif name == "grid_tr_weight":
+            weight(TR0, ".linear1", ".linear2")
+        else:
+            raise KeyError(name)
+
+
+# ----------------------------------------------------------------------------------------------------------------- oracles (float64)
+def _p64(model):
+    return {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()) for k, v in model.state_dict().items()}
+
+
+def oracle_sde(model, cfg, batch, method="euler", ood=False):
+    """the whole SDE model in float64 at the fp32 normals of Philox seed SEED: every stage boundary and output"""
+    import milstein_restate
+    import restate
+    c = restate.flat_cfg(cfg)
+    es, ds = _schedules(cfg)
+    P, b = _p64(model), H.double_batch(batch)
+    noise = H.Float64Noise(restate.PhiloxNoise(SEED))
+    with torch.no_grad():
+        rot, _ = restate.rotate_inputs(b)
+        if ood:
+            local, stds = restate.local_encoder_ood(P, c, b, rot, noise, es)
+            out = dict(stds=stds)
+        else:
+            local, diff_in, diff_out, _ = restate.local_encoder(P, c, b, rot, noise, es)
+            out = dict(diff_in=diff_in, diff_out=diff_out)
+        glob = restate.global_interactor(P, c, b, rot, local)
+        dec = (milstein_restate.sde_decoder(P, c, b, local, glob, noise, ds) if method == "milstein"
+               else restate.sde_decoder(P, c, b, local, glob, noise, ds))
+    out.update(local_embed=local, global_embed=glob, loc=dec["loc"], pi=dec["pi"])
+    return out
+
+
+def oracle_grid(model, cfg, batch):
+    import restate_grid
+    out = restate_grid.forward(_p64(model), cfg, H.double_batch(batch), want_intermediates=True)
+    return {k: out[k] for k in ("local_embed", "global_embed", "loc", "pi")}
+
+
+def ratios(got, want):
+    """{tensor: max|got - want| / (REL * max(1, max|want|))}: the under-the-limit rule, 1.0 is the bound"""
+    out = {}
+    for k, g in got.items():
+        w = want[k].detach().cpu().double()
+        g = g.detach().cpu().double()
+        assert g.shape == w.shape, (k, g.shape, w.shape)
+        err = float((g - w).abs().max()) if bool(torch.isfinite(g).all()) else float("inf")
+        out[k] = err / (REL * max(1.0, float(w.abs().max())))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------- routes
+# A route runs the planted model (already on the device) and returns {output name: tensor}; every launch it makes happens after the
+# flags were read clean.  `want` tells which oracle outputs the returned names are compared with.
+def _noise():
+    from trajsde_amd.runtime import NoiseSpec
+    return NoiseSpec(seed=SEED)
+
+
+def _keys(out, keys):
+    return {k: out[k] for k in keys}
+
+
+def run_infer(model, cfg, batch, dev):
+    """the inference forward in its default form (sync-free graph stage, default kernel switches)"""
+    with torch.no_grad():
+        return _keys(model(H.clone_batch(batch).to(dev), noise=_noise()), ("loc", "pi", "diff_in", "diff_out"))
+
+
+def run_exact(model, cfg, batch, dev):
+    from trajsde_amd import runtime
+    prev = runtime.set_sync_free(False)
+    try:
+        return run_infer(model, cfg, batch, dev)
+    finally:
+        runtime.set_sync_free(prev)
+
+
+def run_bf16(model, cfg, batch, dev):
+    from trajsde_amd import runtime
+    assert runtime.set_state_storage("bf16") == "fp32"
+    try:
+        return run_infer(model, cfg, batch, dev)
+    finally:
+        runtime.set_state_storage("fp32")
+
+
+def run_ood(model, cfg, batch, dev):
+    model.ood = True
+    try:
+        with torch.no_grad():
+            return _keys(model(H.clone_batch(batch).to(dev), noise=_noise()), ("loc", "pi", "stds"))
+    finally:
+        model.ood = False
+
+
+def _rotated(model, batch, dev):
+    data = H.clone_batch(batch).to(dev)
+    model._ensure_rotated(data)
+    return data
+
+
+def run_enc_train(model, cfg, batch, dev):
+    """trajsde_encoder_forward_train, then both backward entry points with tape_valid = 0: each recomputes the forward inside"""
+    data = _rotated(model, batch, dev)
+    rt = model.encoder._rt
+    with torch.no_grad():
+        (local, diff_in, diff_out, _, _), _tape = rt.encoder_forward_train(data, _noise())
+    return dict(local_embed=local, diff_in=diff_in, diff_out=diff_out)
+
+
+def run_enc_bwd(model, cfg, batch, dev):
+    data = _rotated(model, batch, dev)
+    rt = model.encoder._rt
+    d_local = torch.randn(batch.num_nodes, 64, generator=torch.Generator().manual_seed(2)).to(dev)
+    res = rt.encoder_backward(data, d_local, _noise(), diff_weight=0.5, tape=None)
+    return {"grads": res["grads"].flat}
+
+
+def run_enc_cot_bwd(model, cfg, batch, dev):
+    data = _rotated(model, batch, dev)
+    rt = model.encoder._rt
+    d_local = torch.randn(batch.num_nodes, 64, generator=torch.Generator().manual_seed(2)).to(dev)
+    res = rt.encoder_cotangent_backward(data, d_local, None, None, _noise(), tape=None)
+    return {"grads": res["grads"].flat}
+
+
+def _agg_inputs(model, cfg, batch, dev):
+    """the aggregator alone: the graph context comes from an encoder call of the UNPLANTED encoder; local_embed is the oracle's"""
+    data = _rotated(model, batch, dev)
+    with torch.no_grad():
+        model.encoder(data=data, noise=_noise())
+    local = oracle_sde(model, cfg, batch)["local_embed"].float().to(dev)
+    st, mask, _ = read_flags(1)
+    assert mask == 0, names_of(mask)
+    return data, local
+
+
+def run_agg_train(model, cfg, batch, dev):
+    data, local = _agg_inputs(model, cfg, batch, dev)
+    with torch.no_grad():
+        glob, _tape = model.aggregator._rt.aggregator_forward_train(data, local, _noise())
+    return dict(global_embed=glob)
+
+
+def run_agg_bwd(model, cfg, batch, dev):
+    data, local = _agg_inputs(model, cfg, batch, dev)
+    d_glob = torch.randn(K, batch.num_nodes, 64, generator=torch.Generator().manual_seed(3)).to(dev)
+    res = model.aggregator._rt.aggregator_backward(data, local, d_glob, _noise(), tape=None)
+    return {"grads": res["grads"].flat, "d_local_embed": res["d_local_embed"]}
+
+
+def run_agg_legacy(model, cfg, batch, dev):
+    """trajsde_aggregator_forward, the entry point without the heads argument (8 heads)"""
+    from trajsde_amd import _lib, runtime
+    data, local = _agg_inputs(model, cfg, batch, dev)
+    m = model.aggregator
+    gc = runtime.GraphContext.get(data, None, int(m.historical_steps), None, exact=None)
+    L = _lib.lib()
+    out = torch.empty(K, gc.batch.N, 64, device=dev)
+    ws_bytes = L.trajsde_aggregator_ws_bytes(C.byref(gc.batch), C.byref(gc.graph), K)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    assert int(m.num_heads) == 8
+    _lib.check(L.trajsde_aggregator_forward(C.byref(gc.batch), C.byref(gc.graph), m._rt.blob().data_ptr(), int(m.num_layers), K,
+                                            local.data_ptr(), ws.data_ptr(), ws_bytes, out.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), "trajsde_aggregator_forward")
+    return dict(global_embed=out)
+
+
+def _embeddings(N, v, dev):
+    """caller-made decoder inputs: one element of local_embed holds the magnitude (`v` None: none does).  (The welded and the
+    winner-only backward read global_embed in each actor's winning mode only; an actor's row of local_embed is read whatever wins.)"""
+    g = torch.Generator().manual_seed(100 + N)
+    local, glob = torch.randn(N, 64, generator=g), torch.randn(K, N, 64, generator=g)
+    if v is not None:
+        local[3, J] = v
+    return local, glob
+
+
+def run_dec_stage(which):
+    """the SDE decoder's entry points on caller-made embeddings; `which`: forward | l2 | nll | cot | sel.  The backward entry points get
+    the forward's output, and the flag the forward raised is read (and must be the same) before the backward runs"""
+    def run(model, cfg, batch, dev, v=None, expect=None):
+        data = _rotated(model, batch, dev)
+        N = batch.num_nodes
+        local, glob = (t.to(dev) for t in _embeddings(N, v, dev))
+        rt = model.decoder._rt
+        with torch.no_grad():
+            out = rt.decoder_forward(data, local, glob, _noise())
+        if which == "forward":
+            return dict(loc=out["loc"], pi=out["pi"], _local=local, _glob=glob)
+        st, mask, _ = read_flags(1)
+        if expect is not None:
+            assert mask == expect, (names_of(mask), names_of(expect))
+        g = torch.Generator().manual_seed(5)
+        d_loc, d_pi = torch.randn(K, N, T, 4, generator=g).to(dev), torch.randn(N, K, generator=g).to(dev)
+        if which == "l2":
+            res = rt.decoder_l2_backward(data, local, glob, out, _noise())
+        elif which == "nll":
+            res = rt.decoder_nll_backward(data, local, glob, out, _noise(), eps=1e-6)
+        elif which == "cot":
+            res = rt.decoder_cotangent_backward(data, local, glob, out, _noise(), d_loc, d_pi)
+        else:
+            d_loc[1] = 0.0                                                    # one supported mode per actor
+            res = rt.decoder_cotangent_backward(data, local, glob, out, _noise(), d_loc, d_pi, support="winner")
+        return {"grads": res["grads"].flat, "d_local_embed": res["d_local_embed"], "d_global_embed": res["d_global_embed"]}
+    return run
+
+
+def run_grid(model, cfg, batch, dev):
+    with torch.no_grad():
+        out = model(H.clone_batch(batch).to(dev))
+    return _keys(out, ("loc", "pi"))
+
+
+def run_grid_plain_encoder(model, cfg, batch, dev):
+    """trajsde_encoder_grid_forward, the entry point without the dropout argument (the runtime calls the _train one)"""
+    from trajsde_amd import _lib, runtime
+    data = _rotated(model, batch, dev)
+    m = model.encoder
+    gc = runtime.GraphContext.get(data, float(m.local_radius), int(m.historical_steps), runtime.NoiseSpec(seed=0), fake_agents=False)
+    L = _lib.lib()
+    local = torch.empty(gc.batch.N, 64, device=dev)
+    ws_bytes = L.trajsde_encoder_grid_ws_bytes(C.byref(gc.batch), C.byref(gc.graph))
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    _lib.check(L.trajsde_encoder_grid_forward(C.byref(gc.batch), C.byref(gc.graph), gc.rot.data_ptr(), m._rt.blob().data_ptr(),
+                                              int(m.num_heads), int(m.num_temporal_layers), ws.data_ptr(), ws_bytes, local.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream), "trajsde_encoder_grid_forward")
+    return dict(local_embed=local)
+
+
+def run_grid_enc_bwd(train):
+    """trajsde_encoder_grid_backward[_train]: both recompute the forward"""
+    def run(model, cfg, batch, dev):
+        from trajsde_amd import _lib, runtime
+        data = _rotated(model, batch, dev)
+        m = model.encoder
+        rt = m._rt
+        d_local = torch.randn(batch.num_nodes, 64, generator=torch.Generator().manual_seed(2)).to(dev)
+        if train:
+            return {"grads": rt.encoder_grid_backward(data, d_local)["grads"].flat}
+        gc = runtime.GraphContext.get(data, float(m.local_radius), int(m.historical_steps), runtime.NoiseSpec(seed=0), fake_agents=False)
+        L = _lib.lib()
+        nl = int(m.num_temporal_layers)
+        grads = rt._grad_buffers(_lib.STAGE_ENCODER_GRID_BWD)
+        arr, _keep = grads.pointer_array()
+        ws_bytes = L.trajsde_encoder_grid_backward_ws_bytes(C.byref(gc.batch), C.byref(gc.graph), nl)
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        _lib.check(L.trajsde_encoder_grid_backward(C.byref(gc.batch), C.byref(gc.graph), gc.rot.data_ptr(), rt.blob().data_ptr(),
+                                                   rt.blob(_lib.STAGE_ENCODER_GRID_BWD).data_ptr(), int(m.num_heads), nl, d_local.data_ptr(),
+                                                   ws.data_ptr(), ws_bytes, arr, len(grads), torch.cuda.current_stream().cuda_stream),
+                   "trajsde_encoder_grid_backward")
+        return {"grads": grads.flat}
+    return run
+
+
+def run_mlp_stage(which):
+    """the MLP decoder's entry points on caller-made embeddings; `which`: forward | l2 | nll | cot"""
+    def run(model, cfg, batch, dev, v=None, expect=None):
+        data = _rotated(model, batch, dev)
+        N = batch.num_nodes
+        local, glob = (t.to(dev) for t in _embeddings(N, v, dev))
+        rt = model.decoder._rt
+        with torch.no_grad():
+            out = rt.mlp_decoder_forward(data, local, glob)
+        if which == "forward":
+            return dict(loc=out["loc"], pi=out["pi"], _local=local, _glob=glob)
+        st, mask, _ = read_flags(1)
+        if expect is not None:
+            assert mask == expect, (names_of(mask), names_of(expect))
+        g = torch.Generator().manual_seed(5)
+        if which == "l2":
+            res = rt.mlp_decoder_l2_backward(data, local, glob, out)
+        elif which == "nll":
+            res = rt.mlp_decoder_nll_backward(data, local, glob, out, eps=1e-6)
+        else:
+            res = rt.mlp_decoder_cotangent_backward(data, local, glob, out, torch.randn(K, N, T, 4, generator=g).to(dev),
+                                                    torch.randn(N, K, generator=g).to(dev))
+        return {"grads": res["grads"].flat, "d_local_embed": res["d_local_embed"], "d_global_embed": res["d_global_embed"]}
+    return run
+
+
+def run_training_step(model, cfg, batch, dev):
+    """the model-level step: both training forwards, the decoder forward and the three backward entry points on their tapes"""
+    model.loss_weights = [1.0, 0.5]
+    for p in model.parameters():
+        p.grad = None
+    loss = model.training_step(H.clone_batch(batch).to(dev), 0, noise=_noise())
+    loss.backward()
+    return {"loss": loss.detach().reshape(1)}
+
+
+# ----------------------------------------------------------------------------------------------------------------- the table
+class Case:
+    """one cell: `plant` (a name `plant` knows, or None: the route plants an embedding element itself), the route's runner, which model, the
+    bits the cell expects beside its own site's (downstream sites, listed explicitly), and whether the outputs have an oracle"""
+
+    def __init__(self, plant, run, model="sde", extra=(), compare=True, entry=(), note="", inf=True):
+        self.plant, self.run, self.model, self.extra, self.compare, self.entry, self.note = plant, run, model, tuple(extra), compare, tuple(entry), note
+        self.inf = inf                      # False: +inf does not reach the site as +inf on this route (the cell's `note` says why)
+
+
+ROUTES = ("infer", "exact", "node_fp32=0", "node_fp32=1", "alt", "train_fwd", "bwd_recompute", "ood", "milstein", "bf16",
+          "vanilla_fwd", "vanilla_bwd")
+# the child-process routes: environment of the child (tests/range_guard_child.py runs the `infer` cell of every site under it)
+ALT = "<alt>"
+CHILD_FORMS = {
+    "node_fp32=0": [("node_fp32=0", {"TRAJSDE_NODE_FP32": "0"})],
+    "node_fp32=1": [("node_fp32=1", {"TRAJSDE_NODE_FP32": "1"})],
+    # the alternative library's forms (test_gpu_trained_weights._ALT_MODES): other edge-attention and global-attention kernels in front
+    # of the same node block
+    "alt": [(m, dict(e, TRAJSDE_LIB=ALT)) for m, e in (("fused_one_tile", {"TRAJSDE_FUSED_TILES": "1"}), ("gattn_mm", {"TRAJSDE_GATTN_MM": "1"}),
+                                                       ("gattn_two_tiles", {"TRAJSDE_GMF_TILES": "2", "TRAJSDE_REL_SPLIT": "0"}),
+                                                       ("pipelined", {"TRAJSDE_EDGE_PIPE": "1"}), ("tile32", {"TRAJSDE_EDGE_TILE": "32"}),
+                                                       ("tile32_pingpong", {"TRAJSDE_EDGE_TILE": "32", "TRAJSDE_EDGE_PINGPONG": "1"}))],
+}
+IN_CHILD = "in the child process"          # cell marker: the case is the `infer` case of the row, run under CHILD_FORMS[route]
+
+_ENC_ONLY = "the route changes the encoder call only (model forward: encoder.forward_ood); aggregator and decoder are the calls of `infer`"
+_DEC_ONLY = "`method: milstein` changes the decoder's solve only (decoder.hip k_sde_decode<.., MIL>); encoder and aggregator are the calls of `infer`"
+_NO_SDE = "the vanilla variant has no SDE: TemporalEncoder and MLPDecoder keep no state (grid.hip)"
+_INF_NAN = ("+inf not asked for: the global attention forms alpha * v with v split into fp16 pieces, and the low piece of an infinite value is "
+            "inf - inf = NaN -- the aggregate reaches the node block as NaN, which the maximum drops (range.hpp: NaN operands are the consumers')")
+_BF16_ROWS = "the switch changes how rows are stored between kernels (store_row_st), not which kernel notes them; accuracy is not a 1e-4 mode"
+_PACK = "weights are checked by store_split when the image is packed (pack.hip:94), before any kernel of the route runs: the `infer` case"
+
+
+def _same_forward(what):
+    return f"the exact graph stage changes list lengths, not the kernels behind it; run for {what} as the route's cases"
+
+
+TABLE = {
+    "DEC_STATE": {
+        "infer": Case("dec_state", run_infer, entry=("trajsde_decoder_forward",)),
+        "exact": "the exact graph stage changes list lengths, not the decoder (runtime.set_sync_free): the `infer` case",
+        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
+        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
+        "alt": "libtrajsde_alt.so differs in attn.hip, edge32.hip, gattn*.hip, stages.hip (build.ALT_SOURCES): decoder.hip is the same object",
+        "train_fwd": "training runs the inference decoder forward (model._forward_stages): the `infer` case; run_training_step runs it too",
+        "bwd_recompute": Case("dec_state", run_dec_stage("l2"), compare=False,
+                              entry=("trajsde_decoder_l2_backward",), note="k_sde_replay_coop / k_sde_replay note the replayed states"),
+        "ood": _ENC_ONLY,
+        "milstein": Case("dec_state", run_infer, model="milstein", entry=("trajsde_decoder_forward_milstein",)),
+        "bf16": Case("dec_state", run_bf16, compare=False, note=_BF16_ROWS),
+        "vanilla_fwd": _NO_SDE,
+        "vanilla_bwd": _NO_SDE,
+    },
+    "DEC_INPUT": {
+        "infer": Case("dec_input", run_infer),
+        "exact": Case("dec_input", run_exact),
+        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
+        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
+        "alt": "libtrajsde_alt.so differs in attn.hip, edge32.hip, gattn*.hip, stages.hip (build.ALT_SOURCES): decoder.hip is the same object",
+        "train_fwd": Case(None, run_dec_stage("forward"), entry=("trajsde_decoder_forward",)),
+        "bwd_recompute": Case(None, run_dec_stage("cot"), compare=False, entry=("trajsde_decoder_cotangent_backward",),
+                              note="k_init_all; l2 / nll / sel (k_init_sel) in test_decoder_backward_entry_points_refuse_a_large_embedding"),
+        "ood": _ENC_ONLY,
+        "milstein": Case("dec_input", run_infer, model="milstein"),
+        "bf16": Case("dec_input", run_bf16, compare=False, note=_BF16_ROWS),
+        "vanilla_fwd": Case(None, run_mlp_stage("forward"), model="grid", entry=("trajsde_mlp_decoder_forward",)),
+        "vanilla_bwd": Case(None, run_mlp_stage("cot"), model="grid", compare=False, entry=("trajsde_mlp_decoder_cotangent_backward",),
+                            note="k_init_all; l2 / nll (k_init_sel) in test_decoder_backward_entry_points_refuse_a_large_embedding"),
+    },
+    "ENC_STATE": {
+        "infer": Case("enc_state", run_infer, entry=("trajsde_encoder_forward",)),
+        "exact": Case("enc_state", run_exact),
+        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the recurrence does not read it",
+        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the recurrence does not read it",
+        "alt": IN_CHILD,
+        "train_fwd": Case("enc_state", run_enc_train, entry=("trajsde_encoder_forward_train",), note="k_enc_recur_coop<.., save>"),
+        "bwd_recompute": Case("enc_state", run_enc_bwd, compare=False, entry=("trajsde_encoder_backward",)),
+        "ood": Case("enc_state", run_ood, entry=("trajsde_encoder_forward_ood",)),
+        "milstein": _DEC_ONLY,
+        "bf16": Case("enc_state", run_bf16, compare=False, note=_BF16_ROWS),
+        "vanilla_fwd": _NO_SDE,
+        "vanilla_bwd": _NO_SDE,
+    },
+    "ENC_INPUT": {
+        "infer": Case("enc_input", run_infer),
+        "exact": _same_forward("ENC_STATE, DEC_INPUT, NODE_AGG and FFN_HIDDEN"),
+        "node_fp32=0": IN_CHILD,
+        "node_fp32=1": IN_CHILD,
+        "alt": IN_CHILD,
+        "train_fwd": Case("enc_input", run_enc_train),
+        "bwd_recompute": Case("enc_input", run_enc_cot_bwd, compare=False, entry=("trajsde_encoder_cotangent_backward",)),
+        "ood": Case("enc_input", run_ood),
+        "milstein": _DEC_ONLY,
+        "bf16": Case("enc_input", run_bf16, compare=False, note=_BF16_ROWS),
+        "vanilla_fwd": "no recurrence: aa_out goes through k_tr_prep (an add, grid.hip:27) into k_node_proj's LayerNorm (stages.hip:440)",
+        "vanilla_bwd": "no recurrence: aa_out goes through k_tr_prep (an add, grid.hip:27) into k_node_proj's LayerNorm (encoder_bwd.hip:1212)",
+    },
+    "NODE_AGG": {
+        "infer": Case("enc_node_agg", run_infer),
+        "exact": Case("agg_node_agg", run_exact, entry=("trajsde_aggregator_forward_heads",), inf=False, note=_INF_NAN),
+        "node_fp32=0": IN_CHILD,
+        "node_fp32=1": IN_CHILD,
+        "alt": IN_CHILD,
+        "train_fwd": Case("agg_node_agg", run_agg_train, entry=("trajsde_aggregator_forward_train",), inf=False, note="k_node_update<true>; " + _INF_NAN),
+        "bwd_recompute": Case("agg_node_agg", run_agg_bwd, compare=False, entry=("trajsde_aggregator_backward_heads",), inf=False, note=_INF_NAN),
+        "ood": Case("enc_node_agg", run_ood),
+        "milstein": _DEC_ONLY,
+        "bf16": _BF16_ROWS + "; the node block's aggregate never leaves registers",
+        "vanilla_fwd": Case("grid_tr_agg", run_grid, model="grid", entry=("trajsde_encoder_grid_forward_train",), note="grid.hip k_tr_outproj"),
+        "vanilla_bwd": Case("grid_tr_agg", run_grid_enc_bwd(True), model="grid", compare=False, entry=("trajsde_encoder_grid_backward_train",)),
+    },
+    "FFN_HIDDEN": {
+        "infer": Case("enc_ffn", run_infer),
+        "exact": Case("agg_ffn", run_exact),
+        "node_fp32=0": IN_CHILD,
+        "node_fp32=1": IN_CHILD,
+        "alt": IN_CHILD,
+        "train_fwd": Case("agg_ffn", run_agg_train, note="k_ffn6 (aggregator_bwd.hip:1061); the encoder's in test_training_forwards_note_the_ffn"),
+        "bwd_recompute": Case("enc_ffn", run_enc_bwd, compare=False, note="k_ffn6 (encoder_bwd.hip:850)"),
+        "ood": Case("enc_ffn", run_ood),
+        "milstein": _DEC_ONLY,
+        "bf16": _BF16_ROWS + "; the hidden units never leave registers",
+        "vanilla_fwd": Case("grid_tr_ffn", run_grid_plain_encoder, model="grid", entry=("trajsde_encoder_grid_forward",), note="k_ffn (stages.hip:445)"),
+        "vanilla_bwd": Case("grid_tr_ffn", run_grid_enc_bwd(False), model="grid", compare=False, entry=("trajsde_encoder_grid_backward",),
+                            note="k_ffn (encoder_bwd.hip:1218)"),
+    },
+    "WEIGHT": {
+        "infer": Case("agg_weight", run_infer, entry=("trajsde_pack_weights",)),
+        "exact": _PACK,
+        "node_fp32=0": IN_CHILD,
+        "node_fp32=1": IN_CHILD,
+        "alt": IN_CHILD,
+        "train_fwd": Case("agg_weight", run_training_step, compare=False, entry=("trajsde_pack_weights_many",),
+                          note="the step's six images in one packing call (runtime.PackSet)"),
+        "bwd_recompute": _PACK,
+        "ood": _PACK, "milstein": _PACK, "bf16": _PACK,
+        "vanilla_fwd": Case("grid_tr_weight", run_grid, model="grid"),
+        "vanilla_bwd": _PACK,
+    },
+}
+CASES = [(s, r) for s in SITES for r in ROUTES if isinstance(TABLE[s][r], Case)]
+CHILD_CELLS = [(s, r) for s in SITES for r in ROUTES if TABLE[s][r] is IN_CHILD]
+
+
+def test_the_table_has_no_empty_cell():
+    assert set(TABLE) == set(SITES)
+    for s in SITES:
+        assert set(TABLE[s]) == set(ROUTES), s
+        for r, cell in TABLE[s].items():
+            if cell is IN_CHILD:
+                assert r in CHILD_FORMS and isinstance(TABLE[s]["infer"], Case)
+            else:
+                assert isinstance(cell, Case) or (isinstance(cell, str) and len(cell) > 30), (s, r)
+
+
+# ----------------------------------------------------------------------------------------------------------------- running a cell
+_MODELS = {}
+
+
+def fresh_model(kind):
+    """(model on the host, cfg, batch): built once per kind, handed out as a deep copy (a plant writes into the parameters)"""
+    import copy
+    if kind not in _MODELS:
+        model, cfg = grid_model() if kind == "grid" else sde_model("milstein" if kind == "milstein" else "euler")
+        _MODELS[kind] = (model, cfg, sde_batch())
+    model, cfg, batch = _MODELS[kind]
+    return copy.deepcopy(model), cfg, batch
+
+
+def run_cell(site, cell, v, dev):
+    """plant `v`, run the route from clean flags -> (status, mask, message, outputs, planted model, cfg, batch)"""
+    model, cfg, batch = fresh_model(cell.model)
+    if cell.plant is not None:
+        plant(model, cfg, cell.plant, v)
+    model = model.to(dev)
+    st, mask, _ = read_flags(1)
+    assert (st, mask) == (0, 0), names_of(mask)
+    expect = (BIT[site] if v >= LIMIT else 0)
+    out = cell.run(model, cfg, batch, dev, v=v, expect=expect) if cell.plant is None else cell.run(model, cfg, batch, dev)
+    st, mask, msg = read_flags(1)
+    return st, mask, msg, out, model, cfg, batch
+
+
+def oracle_cell(cell, out, model, cfg, batch):
+    if cell.plant is None:                                    # a decoder stage on caller-made embeddings
+        import restate
+        import restate_grid
+        local, glob = out.pop("_local").cpu().double(), out.pop("_glob").cpu().double()
+        P, b = _p64(model), H.double_batch(batch)
+        with torch.no_grad():
+            if cell.model == "grid":
+                return restate_grid.mlp_decoder(P, restate_grid.flat_cfg(cfg), b, local, glob)
+            return restate.sde_decoder(P, restate.flat_cfg(cfg), b, local, glob, H.Float64Noise(restate.PhiloxNoise(SEED)), _schedules(cfg)[1])
+    if cell.model == "grid":
+        return oracle_grid(model, cfg, batch)
+    return oracle_sde(model, cfg, batch, method="milstein" if cell.model == "milstein" else "euler", ood=cell.run is run_ood)
+
+
+def check_cell(site, route, dev, exact_extra=True):
+    """the three checks of one cell -> the under-the-limit ratios.  `exact_extra` False (kernel forms of the child processes, some of
+    which do not have the downstream site): the cell's extra sites may be raised, its own must be"""
+    cell = TABLE[site][route]
+    want_mask = BIT[site]
+    for e in cell.extra:
+        want_mask |= BIT[e]
+    if not fp16x3():
+        want_mask = 0                                          # a bf16x6 build has nothing to guard (range.hpp)
+    # over the limit
+    st, mask, msg, out, *_ = run_cell(site, cell, OVER, dev)
+    if not exact_extra and want_mask and (mask & BIT[site]) and not (mask & ~want_mask):
+        want_mask = mask
+    assert mask == want_mask, f"{site} x {route} at {OVER:g}: sites {names_of(mask)}, expected {names_of(want_mask)}"
+    if want_mask:
+        assert st == UNSUPPORTED and all(WORDS[s] in msg for s in SITES if want_mask & BIT[s]), (st, msg)
+        assert not any(WORDS[s] in msg for s in SITES if not want_mask & BIT[s]), msg
+    # +inf
+    st, mask, msg, out, *_ = run_cell(site, cell, float("inf"), dev)
+    if want_mask and cell.inf:
+        assert st == UNSUPPORTED and mask & BIT[site] and WORDS[site] in msg, f"{site} x {route} at +inf: sites {names_of(mask)}"
+    # under the limit
+    st, mask, msg, out, model, cfg, batch = run_cell(site, cell, UNDER, dev)
+    assert (st, mask) == (0, 0), f"{site} x {route} at {UNDER:g}: sites {names_of(mask)}"
+    for k, t in out.items():
+        assert bool(torch.isfinite(t).all()), (site, route, k)
+    if not cell.compare:
+        print(f"[range-guard] {site} x {route}: flags only ({cell.note})")
+        return {}
+    r = ratios({k: t for k, t in out.items() if not k.startswith("_")}, oracle_cell(cell, out, model, cfg, batch))
+    print(f"[range-guard] {site} x {route} at {UNDER:g}: err / (1e-4 max(1, max|want|)) = " + ", ".join(f"{k} {x:.3f}" for k, x in r.items()))
+    return r
+
+
+@pytest.mark.parametrize("site,route", CASES, ids=[f"{s}-{r}" for s, r in CASES])
+def test_site_by_route(site, route, dev):
+    """one cell of TABLE: 7e4 and +inf are refused with exactly the cell's sites, 6e4 is quiet and matches the float64 oracle"""
+    r = check_cell(site, route, dev)
+    assert all(x <= 1.0 for x in r.values()), r
+
+
+# ----------------------------------------------------------------------------------------------------------------- children
+_CHILD = os.path.join(H.ROOT, "tests", "range_guard_child.py")
+_CHILD_RESULTS = {}
+
+
+def run_child(args, env):
+    from trajsde_amd import _lib
+    env = {k: (_lib.ALT_LIB_PATH if v == ALT else v) for k, v in env.items()}
+    drop = ("TRAJSDE_LIB", "TRAJSDE_NODE_FP32")
+    r = subprocess.run([sys.executable, _CHILD] + list(args), env={**{k: v for k, v in os.environ.items() if k not in drop}, **env},
+                       timeout=600, capture_output=True, text=True)
+    assert r.returncode == 0, f"child {args} {env} failed ({r.returncode}):\n{r.stdout[-3000:]}\n{r.stderr[-6000:]}"
+    for line in r.stdout.splitlines():
+        if line.startswith("[range-guard]"):
+            print(line)
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def child_cells(args):
+    """the `infer` cell -- and the `exact` one, the aggregator's side of the node block, where the row has one -- of each site in `args`,
+    all three checks, in this process (called by tests/range_guard_child.py)"""
+    dev = torch.device("cuda:0")
+    res = {}
+    for site in args:
+        res[site] = check_cell(site, "infer", dev, exact_extra=False)
+        if isinstance(TABLE[site]["exact"], Case):
+            res[site].update({"exact." + k: x for k, x in check_cell(site, "exact", dev, exact_extra=False).items()})
+    return res
+
+
+def _form_results(route, form, env):
+    key = (route, form)
+    if key not in _CHILD_RESULTS:
+        sites = [s for s, r in CHILD_CELLS if r == route]
+        _CHILD_RESULTS[key] = run_child(["cells"] + sites, env)
+    return _CHILD_RESULTS[key]
+
+
+_FORM_IDS = [(route, form, env) for route in CHILD_FORMS for form, env in CHILD_FORMS[route]]
+
+
+@pytest.mark.parametrize("route,form,env", _FORM_IDS, ids=[f"{r}-{f}" for r, f, _ in _FORM_IDS])
+def test_site_by_route_in_a_child_process(route, form, env, dev):
+    """the cells marked IN_CHILD: switches and TRAJSDE_LIB are read once per process, so the `infer` cases of those sites run in one child
+    per kernel form (each asserts like test_site_by_route; a failed assertion ends the child with its traceback)"""
+    res = _form_results(route, form, env)
+    assert set(res["ratios"]) == {s for s, r in CHILD_CELLS if r == route}
+    assert res["fp16x3"] and all(x <= 1.0 for r in res["ratios"].values() for x in r.values()), res
+
+
+# ----------------------------------------------------------------------------------------------------------------- further cases
+@pytest.mark.parametrize("which", ["l2", "nll", "sel", "mlp_l2", "mlp_nll"])
+def test_decoder_backward_entry_points_refuse_a_large_embedding(which, dev):
+    """the recompute at the head of every decoder backward entry point reads the caller's embeddings: k_init_sel (welded and winner-only
+    routes, both decoders) beside the table's k_init_all cells.  The forward's flag is read first; the backward raises its own."""
+    cell = Case(None, run_mlp_stage(which[4:]) if which.startswith("mlp_") else run_dec_stage(which), model="grid" if which.startswith("mlp_") else "sde")
+    for v, want in ((OVER, BIT["DEC_INPUT"]), (float("inf"), BIT["DEC_INPUT"]), (UNDER, 0)):
+        st, mask, msg, out, *_ = run_cell("DEC_INPUT", cell, v, dev)
+        want = want if fp16x3() else 0
+        assert mask == want and (st == UNSUPPORTED) == bool(want), (which, v, names_of(mask), msg)
+        if want:
+            assert WORDS["DEC_INPUT"] in msg
+
+
+def test_milstein_backward_replay_notes_the_state(dev):
+    """trajsde_decoder_l2_backward_milstein / _nll_: k_sde_replay_mil replays the planted drift"""
+    for loss in ("l2", "nll"):
+        cell = Case("dec_state", run_dec_stage(loss), model="milstein", compare=False)
+        for v, want in ((OVER, BIT["DEC_STATE"]), (UNDER, 0)):
+            st, mask, msg, out, *_ = run_cell("DEC_STATE", cell, v, dev)
+            assert mask == (want if fp16x3() else 0), (loss, v, names_of(mask), msg)
+
+
+def test_training_forwards_note_the_ffn(dev):
+    """the encoder's training forward (k_ffn6 of the AA block, encoder_bwd.hip:850), the legacy aggregator entry point and the model-level
+    training step under the FFN plants: the hidden units of the training forwards are watched like the inference ones"""
+    for plant_name, run, compare in (("enc_ffn", run_enc_train, True), ("agg_ffn", run_agg_legacy, True), ("agg_ffn", run_training_step, False),
+                                     ("enc_ffn", run_training_step, False)):
+        cell = Case(plant_name, run, compare=compare)
+        st, mask, msg, *_ = run_cell("FFN_HIDDEN", cell, OVER, dev)
+        assert mask == (BIT["FFN_HIDDEN"] if fp16x3() else 0) and (not mask or WORDS["FFN_HIDDEN"] in msg), (plant_name, run.__name__, names_of(mask))
+        st, mask, msg, out, model, cfg, batch = run_cell("FFN_HIDDEN", cell, UNDER, dev)
+        assert (st, mask) == (0, 0), (plant_name, run.__name__, names_of(mask))
+        if compare:
+            r = ratios(out, oracle_cell(cell, out, model, cfg, batch))
+            print(f"[range-guard] FFN_HIDDEN, {plant_name} through {run.__name__} at {UNDER:g}: " + ", ".join(f"{k} {x:.3f}" for k, x in r.items()))
+            assert all(x <= 1.0 for x in r.values()), r
+
+
+# ----------------------------------------------------------------------------------------------------------------- the threshold itself
+def _sde_step(model, y, dev, bf16=False):
+    from trajsde_amd import _lib
+    from trajsde_amd.schedule import decoder_schedule
+    tab = np.ascontiguousarray(decoder_schedule(T, MAX_T).step_table())
+    e = tab[1].ctypes.data_as(C.POINTER(C.c_float))
+    nz = _lib.Noise(C.c_uint64(3), None, None)
+    out = torch.empty_like(y)
+    _lib.check(_lib.lib().trajsde_sde_step(y.shape[0], model.decoder._rt.blob().data_ptr(), y.data_ptr(), out.data_ptr(), e, 0, C.byref(nz),
+                                           torch.cuda.current_stream().cuda_stream), "trajsde_sde_step")
+    return out
+
+
+@pytest.mark.parametrize("rows", [17, 40])
+def test_the_threshold_is_65504(rows, dev):
+    """trajsde_sde_step on `rows` rows (a ragged tile; two full tiles on the prefetching loop and a ragged one), one element at the
+    threshold: 65504.0 -- the largest finite fp16, which the round-toward-zero split cannot tell from anything above it -- is refused,
+    the largest float below it is not; in the last row, the first, and with either sign"""
+    model, cfg, batch = fresh_model("sde")
+    model = model.to(dev)
+    below = float(np.nextafter(np.float32(LIMIT), np.float32(0)))
+    assert below < LIMIT and np.float32(below) == np.float32(65500.0) + np.float32(3.99609375)
+    read_flags(1)
+    g = torch.Generator().manual_seed(rows)
+    for r, c, sign in ((rows - 1, 63, 1.0), (0, 0, -1.0), (16, 5, 1.0)):
+        for value, flagged in ((below, False), (LIMIT, True)):
+            y = torch.randn(rows, 64, generator=g).to(dev)
+            y[r, c] = sign * value
+            out = _sde_step(model, y, dev)
+            st, mask, msg = read_flags(1)
+            want = BIT["DEC_STATE"] if (flagged and fp16x3()) else 0
+            assert mask == want and (st == UNSUPPORTED) == bool(want), (rows, r, c, sign, value, names_of(mask))
+            assert flagged or bool(torch.isfinite(out).all())
+
+
+# ----------------------------------------------------------------------------------------------------------------- 2. flag semantics
+def test_reset_semantics_and_one_mask_for_all_units(dev):
+    """reset = 0 reports and keeps, reset = 1 reports and clears, the next read is clean; flags raised in different translation units
+    (decoder.hip, recur.hip, attn.hip, pack.hip, grid.hip, decoder_cot_bwd.hip) come back as ONE mask and one message"""
+    model, cfg, batch = fresh_model("sde")
+    model = model.to(dev)
+    read_flags(1)
+    y = torch.full((17, 64), OVER, device=dev)
+    if not fp16x3():                                                    # a bf16x6 build has nothing to raise: the word stays 0
+        _sde_step(model, y, dev)
+        assert read_flags(0)[:2] == (0, 0)
+        return
+    _sde_step(model, y, dev)
+    for _ in range(2):                                                  # reset = 0: still there
+        st, mask, msg = read_flags(0)
+        assert (st, mask) == (UNSUPPORTED, BIT["DEC_STATE"]) and WORDS["DEC_STATE"] in msg
+    st, mask, msg = read_flags(1)                                       # reset = 1 reports it once more ...
+    assert (st, mask) == (UNSUPPORTED, BIT["DEC_STATE"])
+    assert read_flags(0)[:2] == (0, 0) and read_flags(1)[:2] == (0, 0)  # ... and has cleared it
+    from trajsde_amd import _lib
+    _lib.check_range()
+    # sites_out may be null
+    _sde_step(model, y, dev)
+    torch.cuda.synchronize()
+    assert _lib.lib().trajsde_range_status(1, None, torch.cuda.current_stream().cuda_stream) == UNSUPPORTED
+    assert read_flags(1)[:2] == (0, 0)
+    # one mask: grid.hip (the MLP decoder's embedding rows) and decoder_cot_bwd.hip (k_init_all) raise the same bit from two units ...
+    gm, gc, gb = fresh_model("grid")
+    gm = gm.to(dev)
+    run_mlp_stage("cot")(gm, gc, gb, dev, v=OVER)                       # (reads the forward's flag away; the backward's stays)
+    run_mlp_stage("forward")(gm, gc, gb, dev, v=OVER)
+    want = BIT["DEC_INPUT"]
+    # ... decoder.hip (state), recur.hip (encoder state), attn.hip (FFN of the AA block), pack.hip (weight)
+    for name, site in (("enc_state", "ENC_STATE"), ("enc_ffn", "FFN_HIDDEN"), ("agg_weight", "WEIGHT")):
+        m, c, b = fresh_model("sde")
+        plant(m, c, name, OVER)
+        run_infer(m.to(dev), c, b, dev)
+        want |= BIT[site]
+    _sde_step(model, y, dev)
+    want |= BIT["DEC_STATE"]
+    st, mask, msg = read_flags(0)
+    assert (st, mask) == (UNSUPPORTED, want), (names_of(mask), names_of(want))
+    assert all(WORDS[s] in msg for s in SITES if want & BIT[s]) and msg.count("fp16x3 split-precision range exceeded") == 1
+    assert read_flags(1)[1] == want and read_flags(1)[:2] == (0, 0)
+
+
+def test_a_sane_forward_stays_quiet_also_over_nan_filled_memory(dev):
+    """a forward at ordinary magnitudes between two reads raises nothing; neither does one whose workspaces come out of NaN-filled
+    allocator blocks (padded tile lanes read clamped rows, never the memory behind them), nor the training step"""
+    model, cfg, batch = fresh_model("sde")
+    model = model.to(dev)
+    read_flags(1)
+    want = oracle_sde(model, cfg, batch)
+    out = run_infer(model, cfg, batch, dev)
+    assert read_flags(1)[:2] == (0, 0)
+    torch.cuda.synchronize()
+    del out
+    torch.cuda.empty_cache()
+    junk = [torch.full((n,), float("nan"), device=dev) for n in (1 << 22, 1 << 20, 1 << 18, 1 << 16, 1 << 14) for _ in range(3)]
+    torch.cuda.synchronize()
+    del junk                                                            # the caching allocator hands these blocks out again, unwritten
+    out = run_infer(model, cfg, batch, dev)
+    assert read_flags(1)[:2] == (0, 0)
+    r = ratios(out, want)
+    assert all(x <= 1.0 for x in r.values()), r
+    run_training_step(model, cfg, batch, dev)
+    assert read_flags(1)[:2] == (0, 0)
+    gm, gcfg, gb = fresh_model("grid")
+    run_grid(gm.to(dev), gcfg, gb, dev)
+    assert read_flags(1)[:2] == (0, 0)
+
+
+STRICT_SITES = SITES
+
+
+def strict_cells(values):
+    """(child of test_strict_library...) every site's `infer` plant at each of `values`: TRAJSDE_OK, mask 0, the oracle rule"""
+    dev = torch.device("cuda:0")
+    assert not fp16x3()
+    res = {}
+    for site in STRICT_SITES:
+        cell = TABLE[site]["infer"]
+        for v in values:
+            st, mask, msg, out, model, cfg, batch = _strict_run(site, cell, v, dev)
+            assert (st, mask) == (0, 0), (site, v, names_of(mask), msg)
+            r = ratios(out, oracle_cell(cell, out, model, cfg, batch))
+            print(f"[range-guard] strict24 {site} at {v:g}: " + ", ".join(f"{k} {x:.3f}" for k, x in r.items()))
+            res[f"{site}@{v:g}"] = r
+    return res
+
+
+def _strict_run(site, cell, v, dev):
+    model, cfg, batch = fresh_model(cell.model)
+    plant(model, cfg, cell.plant, v)
+    model = model.to(dev)
+    assert read_flags(1)[:2] == (0, 0)
+    out = cell.run(model, cfg, batch, dev)
+    st, mask, msg = read_flags(1)
+    return st, mask, msg, out, model, cfg, batch
+
+
+def test_strict_library_has_fp32_range(dev):
+    """bf16 pieces have fp32's exponent range (range.hpp: the guard is a no-op in the bf16x6 build) -- shown, not said: the over-the-limit
+    plants at 1e5 and 1e8 through variants/libtrajsde_strict24.so return TRAJSDE_OK with mask 0 and match the float64 oracle"""
+    from trajsde_amd import build
+    assert os.path.isfile(build.STRICT_LIB), "variants/libtrajsde_strict24.so is made by build()"
+    res = run_child(["strict", "1e5", "1e8"], {"TRAJSDE_LIB": build.STRICT_LIB})
+    assert not res["fp16x3"] and len(res["ratios"]) == 2 * len(STRICT_SITES)
+    assert all(x <= 1.0 for r in res["ratios"].values() for x in r.values()), res["ratios"]
+
+
+# ----------------------------------------------------------------------------------------------------------------- 3. the lower end
+SCALES = (2.0 ** -60, 2.0 ** -30, 2.0 ** 12, 2.0 ** 40)
+ACTOR_SCALES = (2.0 ** -40, 2.0 ** -20, 1.0, 2.0 ** 10)
+NC, KC, TC = 17, 3, 5                                           # the decoder cotangent cases: K * N = 51 rows, three full tiles and a ragged one
+
+
+def _proportional(tag, got, base, s, rel=2e-6, floor=1e-12):
+    """every tensor of `got` is s times `base` within rel * max|base| + floor (test_gradients_scale_with_the_loss_weights' bound)"""
+    bad = []
+    for k in base:
+        g, b = got[k].detach().cpu().double() / s, base[k].detach().cpu().double()
+        if not bool(torch.isfinite(g).all()) or float((g - b).abs().max()) > rel * float(b.abs().max()) + floor:
+            bad.append((k, float((g - b).abs().max()), float(b.abs().max())))
+    assert not bad, (tag, s, bad)
+
+
+def _actor_scales(N):
+    return torch.tensor([ACTOR_SCALES[n % 4] for n in range(N)], dtype=torch.float32)
+
+
+def compare_grads_floor(tag, got, want, floor, rel=H.BACKWARD_REL):
+    """helpers.compare_grads with the absolute floor `floor` in place of 1e-7 (and no float32-noise widening): the rule that still means
+    something for gradients far below 1e-7"""
+    bad = []
+    for k in sorted(got):
+        g = got[k].detach().cpu().double()
+        w = want.get(k)
+        w = torch.zeros_like(g) if w is None else w.detach().cpu().double()
+        scale, err = float(w.abs().max()), float((g - w).abs().max())
+        if not bool(torch.isfinite(g).all()):
+            bad.append((k, "non-finite"))
+        elif H.zero_by_softmax_symmetry(k):
+            if err > H.KEY_BIAS_ABS or scale > H.KEY_BIAS_ABS:
+                bad.append((k, err, scale))
+        elif err > rel * scale + floor:
+            bad.append((k, err, scale))
+    print(f"[range-guard] {tag}: floor {floor:.1e}, {len(got)} tensors, {len(bad)} over")
+    return bad
+
+
+def _dec_all(res):
+    d = dict(res["grads"])
+    d.update(d_local_embed=res["d_local_embed"], d_global_embed=res["d_global_embed"])
+    return {k: v.clone() for k, v in d.items()}
+
+
+@pytest.fixture(scope="module")
+def dec_case(dev):
+    import test_gpu_cotangent as TC_
+    model, cfg, batch, sched, t = TC_._stage_case(NC, KC, TC, dev)
+    from trajsde_amd import runtime
+    noise = runtime.NoiseSpec(z_dec=t["z"].to(dev))
+    data = batch.to(dev)
+    local, glob = t["local"].to(dev), t["glob"].to(dev)
+    rt = model.decoder._rt
+    with torch.no_grad():
+        out = rt.decoder_forward(data, local, glob, noise)
+
+    def call(d_loc, d_pi, support="all"):
+        return _dec_all(rt.decoder_cotangent_backward(data, local, glob, out, noise, d_loc.to(dev), d_pi.to(dev), support=support))
+    return dict(model=model, cfg=cfg, batch=batch, sched=sched, t=t, call=call)
+
+
+@pytest.fixture(scope="module")
+def mlp_case(dev):
+    import test_gpu_grid_cotangent as TG
+    model, cfg, batch, t = TG._stage_case(NC, KC, TC, dev)
+    data = batch.to(dev)
+    local, glob = t["local"].to(dev), t["glob"].to(dev)
+    rt = model.decoder._rt
+    with torch.no_grad():
+        out = rt.mlp_decoder_forward(data, local, glob)
+
+    def call(d_loc, d_pi, support="all"):
+        return _dec_all(rt.mlp_decoder_cotangent_backward(data, local, glob, out, d_loc.to(dev), d_pi.to(dev)))
+    return dict(model=model, cfg=cfg, batch=batch, t=t, call=call)
+
+
+def _winner_only(d_loc):
+    """a cotangent with one supported mode per actor (mode n % K), as a winner-takes-all loss leaves it"""
+    keep = torch.zeros(KC, NC, 1, 1)
+    keep[torch.arange(NC) % KC, torch.arange(NC)] = 1.0
+    return d_loc * keep
+
+
+@pytest.mark.parametrize("entry", ["dense", "sel", "mlp"])
+def test_decoder_cotangents_uniform_scale(entry, dec_case, mlp_case):
+    """d_loc, d_pi scaled by 2^-60 .. 2^40: every returned tensor is that power of two times the s = 1 result"""
+    case = mlp_case if entry == "mlp" else dec_case
+    d_loc, d_pi = case["t"]["d_loc"], case["t"]["d_pi"]
+    support = "winner" if entry == "sel" else "all"
+    if entry == "sel":
+        d_loc = _winner_only(d_loc)
+    base = case["call"](d_loc, d_pi, support)
+    assert all(float(v.abs().max()) > 0 for k, v in base.items() if k.startswith("d_"))
+    for s in SCALES:
+        _proportional(f"{entry} uniform", case["call"](d_loc * s, d_pi * s, support), base, s)
+    assert read_flags(1)[:2] == (0, 0)
+
+
+@pytest.mark.parametrize("entry", ["dense", "sel", "mlp"])
+def test_decoder_cotangents_per_actor_scale(entry, dec_case, mlp_case):
+    """s_n from {2^-40, 2^-20, 1, 2^10} cyclically over the actors, so every 16-row tile and 64-row weight-gradient block mixes all four:
+    rows of the decoder do not interact, so row n of d_local_embed and of d_global_embed[:, n] is s_n times the base row within 2e-6 of
+    THAT ROW's maximum (a product scaled per tile instead of per row fails here); the parameter gradients of the same call against
+    float64 autograd under the scaled cotangents (helpers.compare_grads)"""
+    import restate
+    case = mlp_case if entry == "mlp" else dec_case
+    t = case["t"]
+    d_loc, d_pi = t["d_loc"], t["d_pi"]
+    support = "winner" if entry == "sel" else "all"
+    if entry == "sel":
+        d_loc = _winner_only(d_loc)
+    s = _actor_scales(NC)
+    base = case["call"](d_loc, d_pi, support)
+    d_loc_s, d_pi_s = d_loc * s[None, :, None, None], d_pi * s[:, None]
+    got = case["call"](d_loc_s, d_pi_s, support)
+    s64 = s.double()
+    for k, per_row in (("d_local_embed", s64[:, None]), ("d_global_embed", s64[None, :, None])):
+        g, b = got[k].cpu().double() / per_row, base[k].cpu().double()
+        assert bool(torch.isfinite(g).all()), k
+        row_max = b.abs().amax(-1, keepdim=True)
+        over = (g - b).abs() - (2e-6 * row_max + 1e-30)
+        assert float(over.max()) <= 0.0, (entry, k, float(over.max()), int((over > 0).sum()))
+    ts = dict(t, d_loc=d_loc_s, d_pi=d_pi_s)
+    if entry == "mlp":
+        import test_gpu_grid_cotangent as TG
+        want = TG._oracle_vjp(case["model"], case["cfg"], case["batch"], ts)
+    else:
+        import test_gpu_cotangent as TC_
+        want = TC_._oracle_vjp(case["model"], case["cfg"], case["batch"], case["sched"], ts, restate.InjectedNoise(None, None, t["z"]))
+    bad = H.compare_grads(f"range-guard, {entry} per-actor scales", got, {k: want.get(k) for k in got})
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("entry", ["dense", "sel", "mlp"])
+def test_decoder_cotangents_zero_rows(entry, dec_case, mlp_case):
+    """actors whose cotangents are exactly zero, next to live ones in every tile: exactly zero rows back, nothing non-finite"""
+    case = mlp_case if entry == "mlp" else dec_case
+    d_loc, d_pi = case["t"]["d_loc"].clone(), case["t"]["d_pi"].clone()
+    support = "winner" if entry == "sel" else "all"
+    if entry == "sel":
+        d_loc = _winner_only(d_loc)
+    dead = torch.arange(NC) % 3 == 1
+    d_loc[:, dead] = 0.0
+    d_pi[dead] = 0.0
+    got = case["call"](d_loc, d_pi, support)
+    assert all(bool(torch.isfinite(v).all()) for v in got.values())
+    assert float(got["d_local_embed"][dead].abs().max()) == 0.0 and float(got["d_global_embed"][:, dead].abs().max()) == 0.0
+    assert float(got["d_local_embed"][~dead].abs().min(0).values.max()) > 0.0
+
+
+# -- the encoder entry point and the stage nodes: rows mix through attention, so float64 autograd is the reference
+@pytest.fixture(scope="module")
+def enc_case(dev):
+    import test_gpu_stage_autograd as SA
+    Kc, Tc, max_t, make = SA.CASES["n17_k3_t5"]
+    model, cfg = SA._model(Kc, Tc, max_t)
+    batch = make()
+    N, A = batch.num_nodes, int(batch["agent_index"].numel())
+    g = torch.Generator().manual_seed(8)
+    cots = dict(local_embed=torch.randn(N, 64, generator=g), diff_in=torch.randn(A, 64, generator=g), diff_out=torch.randn(A, 64, generator=g))
+    model = model.to(dev)
+    data = H.clone_batch(batch).to(dev)
+    model._ensure_rotated(data)
+    from trajsde_amd.runtime import NoiseSpec
+    noise = NoiseSpec(seed=SA.SEED)
+    rt = model.encoder._rt
+
+    def call(c):
+        res = rt.encoder_cotangent_backward(data, c["local_embed"].to(dev), c["diff_in"].to(dev), c["diff_out"].to(dev), noise, tape=None,
+                                            want_boundaries=True)
+        d = {"encoder." + k: v.clone() for k, v in res["grads"].items()}
+        d.update(d_latent=res["d_latent"].clone(), d_aa_out=res["d_aa_out"].clone())
+        return d
+
+    def oracle(c):
+        _, want = SA._oracle(model, cfg, batch, SA._cotangent_loss(c), upto="encoder")
+        return want
+    return dict(model=model, cfg=cfg, batch=batch, cots=cots, call=call, oracle=oracle, N=N, A=A, SA=SA)
+
+
+def test_encoder_cotangents_uniform_scale(enc_case):
+    """trajsde_encoder_cotangent_backward with cotangents of local_embed, diff_in and diff_out scaled by 2^-60 .. 2^40"""
+    base = enc_case["call"](enc_case["cots"])
+    assert float(base["d_aa_out"].abs().max()) > 0
+    for s in SCALES:
+        _proportional("encoder uniform", enc_case["call"]({k: v * s for k, v in enc_case["cots"].items()}), base, s)
+    assert read_flags(1)[:2] == (0, 0)
+
+
+def test_encoder_cotangents_per_actor_scale(enc_case):
+    """per-actor scales on the rows of d_local (and per-agent ones on the diffusion cotangents): against float64 autograd under the same
+    cotangents, by helpers.compare_grads and by the same rule with the floor 1e-7 * min_n s_n"""
+    N, A = enc_case["N"], enc_case["A"]
+    s = _actor_scales(N)
+    c = {"local_embed": enc_case["cots"]["local_embed"] * s[:, None], "diff_in": enc_case["cots"]["diff_in"] * _actor_scales(A)[:, None],
+         "diff_out": enc_case["cots"]["diff_out"] * _actor_scales(A)[:, None]}
+    got = enc_case["call"](c)
+    got = {k: v for k, v in got.items() if k.startswith("encoder.")}
+    want = enc_case["oracle"](c)
+    assert all(bool(torch.isfinite(v).all()) for v in got.values())
+    bad = H.compare_grads("range-guard, encoder per-actor scales", got, want)
+    assert not bad, bad
+    bad = compare_grads_floor("encoder per-actor scales", got, want, 1e-7 * min(ACTOR_SCALES))
+    assert not bad, bad
+
+
+def test_encoder_cotangents_zero_rows(enc_case):
+    """actors whose row of d_local is exactly zero (and no diffusion cotangent at all): no NaN; with EVERY cotangent zero, exactly zero"""
+    N, A = enc_case["N"], enc_case["A"]
+    dead = torch.arange(N) % 3 == 1
+    c = {"local_embed": enc_case["cots"]["local_embed"].clone(), "diff_in": torch.zeros(A, 64), "diff_out": torch.zeros(A, 64)}
+    c["local_embed"][dead] = 0.0
+    got = enc_case["call"](c)
+    assert all(bool(torch.isfinite(v).all()) for v in got.values())
+    want = enc_case["oracle"](c)
+    bad = H.compare_grads("range-guard, encoder zero rows", {k: v for k, v in got.items() if k.startswith("encoder.")}, want)
+    assert not bad, bad
+    zero = enc_case["call"]({k: torch.zeros_like(v) for k, v in c.items()})
+    assert all(float(v.abs().max()) == 0.0 for v in zero.values())
+
+
+def _stage_step(enc_case, dev, weights):
+    """one pass through the three stage_autograd nodes under sum_n w_n * (a fixed random functional of actor n's loc and pi) plus
+    the diffusion outputs' functional: (gradients, float64 autograd's)"""
+    SA = enc_case["SA"]
+    model, cfg, batch = enc_case["model"], enc_case["cfg"], enc_case["batch"]
+    N, A = enc_case["N"], enc_case["A"]
+    Kc, Tc = 3, 5
+    g = torch.Generator().manual_seed(12)
+    # (2^-6 randn: with the actor scales up to 2^10 on top, the key biases' rounding noise stays under compare_grads' ABSOLUTE 5e-5)
+    c_loc, c_pi = torch.randn(Kc, N, Tc, 4, generator=g) / 64, torch.randn(N, Kc, generator=g) / 64
+    c_in, c_out = torch.randn(A, 64, generator=g) / 64, torch.randn(A, 64, generator=g) / 64
+    w = weights
+
+    def loss_fn(data, out):
+        dv, dt = out["loc"].device, out["loc"].dtype
+        wn = w.to(dv, dt)
+        return ((out["loc"] * c_loc.to(dv, dt)).sum((0, 2, 3)) * wn).sum() + ((out["pi"] * c_pi.to(dv, dt)).sum(1) * wn).sum() + \
+            float(w.min()) * ((out["diff_in"] * c_in.to(dv, dt)).sum() + (out["diff_out"] * c_out.to(dv, dt)).sum())
+    _, got, _ = SA._step(model, batch, dev, loss_fn)
+    _, want = SA._oracle(model, cfg, batch, loss_fn)
+    return got, want
+
+
+def test_stage_nodes_uniform_and_per_actor_scale(enc_case, dev):
+    """encoder -> aggregator -> decoder through the stage_autograd nodes under a loss whose per-actor weights are (a) one power of two,
+    2^-60 .. 2^40: the gradients are that power times the weight-1 ones; (b) the cyclic per-actor scales: float64 autograd, by
+    compare_grads and with the floor 1e-7 * min_n s_n"""
+    N = enc_case["N"]
+    base, _ = _stage_step(enc_case, dev, torch.ones(N))
+    assert len(base) > 100
+    for s in SCALES:
+        got, _ = _stage_step(enc_case, dev, torch.full((N,), s))
+        assert set(got) == set(base)
+        _proportional("stage nodes uniform", got, base, s)
+    got, want = _stage_step(enc_case, dev, _actor_scales(N))
+    assert all(bool(torch.isfinite(v).all()) for v in got.values())
+    bad = H.compare_grads("range-guard, stage nodes per-actor scales", got, want)
+    assert not bad, bad
+    bad = compare_grads_floor("stage nodes per-actor scales", got, want, 1e-7 * min(ACTOR_SCALES))
+    assert not bad, bad
+    assert read_flags(1)[:2] == (0, 0)
+
+
+# ----------------------------------------------------------------------------------------------------------------- accounting
+# launching entry points of include/*.h that form no split-precision product on caller-controlled data, each with its reason
+NO_PRODUCT = {
+    "trajsde_rotate": "sin / cos and a 2 x 2 product per row in plain fp32 (prep.hip); no matrix-core product",
+    "trajsde_graph_prepare": "builds index lists and edge geometry (prep.hip); no matrix-core product",
+    "trajsde_graph_prepare_async": "builds index lists and edge geometry (prep.hip); no matrix-core product",
+    "trajsde_graph_compact": "copies index lists (prep.hip); no arithmetic on features",
+    "trajsde_grad_gather_add": "gathers and adds gradient words (optim.hip); no product",
+    "trajsde_adamw_step": "element-wise fp32 update (optim.hip); no product",
+    "trajsde_grad_norm_clip": "fp32 / fp64 sum of squares (clip.hip); no product",
+    "trajsde_adamw_step_clipped": "element-wise fp32 update (clip.hip); no product",
+    "trajsde_encoder_fork_stream": "records an event and makes a stream wait; no kernel",
+    "trajsde_aggregator_prepare": "the relative-pose embedding alone (k_edge_embed2): inputs are LayerNorm outputs, the stored rows "
+                                  "are bounded by sqrt(63) |gamma| + |beta| (attn.hip, at store_tile_rows_split)",
+    "trajsde_aggregator_forward_prepared": "trajsde_aggregator_forward_heads behind trajsde_aggregator_prepare (TRAJSDE_OVERLAP_REL=1, off by "
+                                           "default): the same node kernels as the NODE_AGG / FFN_HIDDEN x exact cells",
+    "trajsde_aggregator_backward": "trajsde_aggregator_backward_heads with 8 heads and no dropout (the same function behind it)",
+    "trajsde_range_status": "the reader of the flag words itself; launches nothing",
+    "trajsde_profile_mode": "host-side switch of the event recorder",
+    "trajsde_profile_report": "formats timings into a host buffer",
+    "trajsde_export_senders": "host-side switch of what the graph stage exports",
+    "trajsde_state_storage": "host-side switch (the bf16 column)",
+}
+# entry points exercised by the tests of this module outside TABLE's `entry` lists: name -> test
+ELSEWHERE = {
+    "trajsde_sde_step": "test_the_threshold_is_65504",
+    "trajsde_aggregator_forward": "test_training_forwards_note_the_ffn",
+    "trajsde_aggregator_forward_heads": "TABLE NODE_AGG x exact",
+    "trajsde_decoder_nll_backward": "test_decoder_backward_entry_points_refuse_a_large_embedding",
+    "trajsde_decoder_cotangent_backward_sel": "test_decoder_backward_entry_points_refuse_a_large_embedding",
+    "trajsde_mlp_decoder_l2_backward": "test_decoder_backward_entry_points_refuse_a_large_embedding",
+    "trajsde_mlp_decoder_nll_backward": "test_decoder_backward_entry_points_refuse_a_large_embedding",
+    "trajsde_decoder_l2_backward_milstein": "test_milstein_backward_replay_notes_the_state",
+    "trajsde_decoder_nll_backward_milstein": "test_milstein_backward_replay_notes_the_state",
+}
+
+
+def header_entry_points():
+    names = set()
+    inc = os.path.join(H.ROOT, "include")
+    for f in sorted(os.listdir(inc)):
+        if f.endswith(".h"):
+            with open(os.path.join(inc, f)) as fh:
+                names |= set(re.findall(r"^(?:int|int64_t|float|const char\*) (trajsde_\w+)\(", fh.read(), flags=re.M))
+    return names
+
+
+def table_entry_points():
+    return {e for s in SITES for r in ROUTES if isinstance(TABLE[s][r], Case) for e in TABLE[s][r].entry}
+
+
+def test_zz_every_launch_entry_point_is_accounted_for(dev):
+    """every function of the C-ABI headers under include/ is a host-only query, or named by a cell of TABLE (or a test of this module),
+    or left out with a reason; and the ones named were really called when the whole module ran"""
+    names = header_entry_points()
+    assert len(names) > 70 and "trajsde_encoder_cotangent_backward" in names and "trajsde_sde_step" in names
+    queries = {n for n in names if n.endswith("_bytes")} | {"trajsde_last_error", "trajsde_split_products", "trajsde_abi_version",
+                                                            "trajsde_param_count", "trajsde_param_name", "trajsde_blob_floats",
+                                                            "trajsde_sync_free_supported", "trajsde_radius2_threshold"}
+    covered = table_entry_points() | set(ELSEWHERE)
+    assert not (covered | set(NO_PRODUCT) | queries) - names, sorted((covered | set(NO_PRODUCT) | queries) - names)
+    assert not covered & set(NO_PRODUCT)
+    unaccounted = names - queries - covered - set(NO_PRODUCT)
+    assert not unaccounted, f"entry points without a range-guard cell or a reason: {sorted(unaccounted)}"
+    assert all(len(r) > 20 for r in NO_PRODUCT.values())
+    if RAN >= {n for n, f in globals().items() if n.startswith("test_") and callable(f)} - {"test_zz_every_launch_entry_point_is_accounted_for"}:
+        missed = sorted(covered - CALLED)                      # (the whole module ran, not a selection of it)
+        print(f"[range-guard] {len(covered)} entry points in the table, {len(covered & CALLED)} called in this run")
+        assert not missed, f"named by the table but never called: {missed}"

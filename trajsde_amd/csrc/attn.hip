@@ -1101,6 +1101,7 @@ __global__ __launch_bounds__(1024) void k_edge_embed2(const float* __restrict__ 
       if (st_bf16 == 2) {
         // split-precision image (gattn_h3.hip): the row as fp16 hi[64] | fp16 lo[64] -- the operand pieces its three readers would
         // otherwise each form again -- through the same LDS tile, whole rows out
+        // (no range note: nrm is a LayerNorm output times gamma plus beta, |.| <= sqrt(63) |gamma| + |beta| per element)
         store_tile_rows_split(stg + wave * ROWSTAGE, nrm[t], emb_out, pair * 32 + 16 * t, n_edges, L);
       } else if (st_bf16 != 0) {                             // bf16 rows (128 B): stored from the row-on-lane registers as before
         if (e[t] < n_edges) store_row_st(nrm[t], emb_out, e[t], L.g, true);
@@ -1576,6 +1577,7 @@ __global__ __launch_bounds__(512) void k_ffn6(const float* __restrict__ img_g, c
         }
         drop_feat16(mo, drop, DK_OUT, uint32_t(r), 0, L.g);
       }
+      range_note(absmax<8>(hid), RS_FFN_HIDDEN);               // as k_ffn: this half's hidden units are the next product's split operand
       if (hf == 0) {
         load_vec<4>(o, lds + FfnL6::B2, L.g);
         load_row(n, x1, r, L.g);
@@ -1623,6 +1625,8 @@ __global__ __launch_bounds__(512) void k_node_proj(const float* __restrict__ img
       f4 t4[4] = {pr[4 * j], pr[4 * j + 1], pr[4 * j + 2], pr[4 * j + 3]};
 #if TSDE_SPLIT_H3
       if (SPLITKV && j > 0) {
+        // (no range note.  |row| <= sum_i |w_i| (sqrt(63) |gamma_i| + |beta_i|) + |b|: a LayerNorm output through a checked weight, plus a
+        //  plain bias that nothing checks.  A value bias >= 65504 shows downstream as RS_NODE_AGG in k_node_update; a key bias does not.)
         if (row < R) {
           char* o = reinterpret_cast<char*>(outs[j] + row * 64);
 #pragma unroll

@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "layouts.hpp"
 #include "philox.hpp"
+#include "range.hpp"
 #include "sde_funcs.hpp"
 #include "tile.hpp"
 #include "tile_bwd.hpp"
@@ -181,6 +182,7 @@ __global__ __launch_bounds__(128) void k_init_sel(const float* __restrict__ img,
     f4 gl[4], lo[4], a[4];
     load_row(gl, global, int64_t(best[i]) * N + i, L.g);
     load_row(lo, local, i, L.g);
+    range_note(fmaxf(absmax<4>(gl), absmax<4>(lo)), RS_DEC_INPUT);   // the caller's rows: no forward call has to precede a backward one
     load_vec<4>(a, lds + InitBwdL::BA, L.g);
     linear_acc<4, 4>(a, gl, lds + InitBwdL::WA_G, L.lane);
     linear_acc<4, 4>(a, lo, lds + InitBwdL::WA_L, L.lane);
@@ -237,6 +239,7 @@ __global__ __launch_bounds__(128) void k_sde_replay(const float* __restrict__ im
       }
       noise_row(z, na, STREAM_DECODER, k, r, int64_t(N) * K, L.g);
       em_update(y, f, gs, z, dt, sq);
+      range_note(absmax<4>(y), RS_DEC_STATE);                 // as the forward (decoder.hip k_sde_decode): the next step's split operand
       if (row < N) store_row(y, states + (k + 1) * slab, row, L.g);
     }
   }

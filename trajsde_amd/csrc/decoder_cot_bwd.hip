@@ -16,6 +16,7 @@
 // weight gradients with the welded entry points (decoder_bwd_host.hpp, defined in decoder_bwd.hip).
 #include "common.hpp"
 #include "layouts.hpp"
+#include "range.hpp"
 #include "tile.hpp"
 #include "tile_bwd.hpp"
 #include "bwd.hpp"
@@ -39,6 +40,7 @@ __global__ __launch_bounds__(128) void k_init_all(const float* __restrict__ img,
     f4 gl[4], lo[4], a[4];
     load_row(gl, global, r, L.g);
     load_row(lo, local, r % N, L.g);
+    range_note(fmaxf(absmax<4>(gl), absmax<4>(lo)), RS_DEC_INPUT);   // the caller's rows: no forward call has to precede a backward one
     load_vec<4>(a, lds + InitBwdL::BA, L.g);
     linear_acc<4, 4>(a, gl, lds + InitBwdL::WA_G, L.lane);
     linear_acc<4, 4>(a, lo, lds + InitBwdL::WA_L, L.lane);

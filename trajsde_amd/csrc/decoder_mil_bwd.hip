@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "layouts.hpp"
 #include "philox.hpp"
+#include "range.hpp"
 #include "sde_funcs.hpp"
 #include "tile.hpp"
 #include "tile_bwd.hpp"
@@ -66,6 +67,7 @@ __global__ __launch_bounds__(128) void k_sde_replay_mil(const float* __restrict_
       f4 J[4];                                             // GFunc's input gradient without s (1 - s) (sde_funcs.hpp)
       gfunc_input_grad(J, h1, h2, G + DiffL::W4, mil, L);
       milstein_update(y, f, gs, J, z, dt, sq);
+      range_note(absmax<4>(y), RS_DEC_STATE);                 // as the forward (decoder.hip k_sde_decode<.., MIL>)
       if (row < N) store_row(y, states + (k + 1) * slab, row, L.g);
     }
   }

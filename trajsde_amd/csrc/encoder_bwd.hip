@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "layouts.hpp"
 #include "philox.hpp"
+#include "range.hpp"
 #include "sde_funcs.hpp"
 #include "tile.hpp"
 #include "tile_bwd.hpp"
@@ -173,6 +174,7 @@ static __device__ __forceinline__ void enc_sde_save_body(const float* lds, const
     f4 y[4], h1[4], h2[4], f[4], z[4];
     if (h_in != nullptr) load_row(y, h_in, r, L.g);
     else load_vec<4>(y, hidden0, L.g);
+    range_note(absmax<4>(y), RS_ENC_STATE);                    // as recur.hip k_enc_sde_step
     if (live) store_row(y, HIN, off + row, L.g);
     const float* F = lds + EncSdeL::F;
     sde_layer0(h1, y, F, DriftL::W0, DriftL::WS, DriftL::WC, DriftL::B0, sn, cs, L);
@@ -231,6 +233,8 @@ static __device__ __forceinline__ void enc_gru_save_body(const float* lds, const
     f4 h[4], x[4], ur[8];
     load_row(h, HODE, off + r, L.g);
     load_row(x, x_t, r, L.g);
+    range_note(absmax<4>(h), RS_ENC_STATE);                    // as recur.hip k_enc_gru_step
+    range_note(absmax<4>(x), RS_ENC_INPUT);
     load_vec<8>(ur, lds + G::BUR, L.g);
     linear_acc<8, 4>(ur, h, lds + G::WUR_H, L.lane);
     linear_acc<8, 4>(ur, x, lds + G::WUR_X, L.lane);

@@ -17,6 +17,7 @@
 #include "dropout.hpp"
 #include "kernels.hpp"
 #include "layouts.hpp"
+#include "range.hpp"
 #include "tile.hpp"
 
 namespace tsde {
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(512) void k_tr_outproj(const float* __restrict__ im
     const int64_t row = tile * 16 + L.n, r = row < R ? row : R - 1;
     f4 a[4], t[4];
     load_row(a, o, r, L.g);
+    range_note(absmax<4>(a), RS_NODE_AGG);                   // a convex mix of value rows, the value bias in them: not normalised
     linear<4, 4>(t, a, lds + TrOutL::WOUT, lds + TrOutL::BOUT, L);
     if (drop.p > 0.f) {
       f4 mk[4];
@@ -155,6 +157,7 @@ __global__ __launch_bounds__(512) void k_mlp_init(const float* __restrict__ img,
     f4 gl[4], lo[4], a[4], b[4];
     load_row(gl, global, r, L.g);
     load_row(lo, local, r % N, L.g);
+    range_note(fmaxf(absmax<4>(gl), absmax<4>(lo)), RS_DEC_INPUT);      // the caller's rows, unnormalised (as decoder.hip k_dec_init)
     load_vec<4>(a, lds + I::BA, L.g);
     linear_acc<4, 4>(a, gl, lds + I::WA_G, L.lane);
     linear_acc<4, 4>(a, lo, lds + I::WA_L, L.lane);

@@ -7,7 +7,14 @@
 // data-dependent, unnormalised tensors: the SDE states (integrated noise), the rows entering the recurrence from the
 // attention block, the decoder's embedding inputs, the attention aggregates and the FFN hidden units.  Each kernel that
 // feeds such a tensor to a split product notes its magnitude here -- one v_max3 per two values and one compare per tile --
-// and a value >= 65504 (or a NaN) sets a sticky bit in a per-device flag word.  The host reads the word at its natural
+// and a value >= 65504 (+-inf included; a NaN is dropped by the maximum, see range_note) sets a sticky bit in a per-device
+// flag word.  That covers the inference forwards, the training
+// forwards (k_ffn6, the tape-keeping recurrence) and the recomputes at the head of every backward entry point (k_init_sel /
+// k_init_all and the replays of the SDE states), which read caller tensors without a forward call having to precede them.
+// Left unguarded because bounded by construction, each with the bound at the kernel: LayerNorm outputs (at most
+// sqrt(63) |gamma| + |beta| per element) entering a checked weight -- k_node_proj, k_mode_proj, the heads -- and the
+// relative-pose rows stored by store_tile_rows_split (attn.hip k_edge_embed2).  NOT guarded and not bounded: the k_node /
+// v_node rows of a global layer, which carry a plain bias (see attn.hip k_node_proj).  The host reads the word at its natural
 // synchronisation points through trajsde_range_status(): TRAJSDE_ERR_UNSUPPORTED instead of a silently saturated result.
 // Weights are checked once, when their fp16 images are packed.
 //
@@ -24,10 +31,10 @@ namespace tsde {
 
 enum RangeSite : unsigned {
   RS_DEC_STATE = 0,    // decoder SDE state y (DEC:88 solve)
-  RS_DEC_INPUT = 1,    // local / global embedding rows entering aggr_embed / pi (DEC:82, 93)
+  RS_DEC_INPUT = 1,    // local / global embedding rows entering aggr_embed / pi (DEC:82, 93; GDEC:47-50; the backward recomputes)
   RS_ENC_STATE = 2,    // encoder latent state h (ENC:140-182)
   RS_ENC_INPUT = 3,    // aa_out rows entering the GRU (ENC:176)
-  RS_NODE_AGG = 4,     // attention aggregate / gated update entering lin_ih, out_proj (ENC:595-609, AGG:119-131)
+  RS_NODE_AGG = 4,     // attention aggregate / gated update entering lin_ih, out_proj (ENC:595-609, AGG:119-131; GENC:276)
   RS_FFN_HIDDEN = 5,   // ReLU(mlp.0(..)) entering mlp.3
   RS_WEIGHT = 6,       // a weight whose fp16 image would overflow
   RS_SITES = 7

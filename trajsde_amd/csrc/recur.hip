@@ -980,6 +980,7 @@ __global__ __launch_bounds__(256) void k_sde_replay_coop(const float* __restrict
     const int64_t r = int64_t(best[i]) * N + i;
     const uint32_t rid = na.row_ids ? uint32_t(na.row_ids[r]) : uint32_t(r);
     f4 y = *reinterpret_cast<const f4*>(states + int64_t(i) * D + ch);
+    float m_state = 0.f;                                 // fp16 range guard (range.hpp): running maximum, noted once behind the loop
     lds_barrier();                                       // the previous tile's readers of the operand tiles are done
     opnd_write(Yop, y, w, L);
     for (int k = 0; k < n_euler; ++k) {
@@ -1041,12 +1042,14 @@ __global__ __launch_bounds__(256) void k_sde_replay_coop(const float* __restrict
       const float gs = fast_sigmoid(((dotp[L.n] + dotp[16 + L.n]) + (dotp[32 + L.n] + dotp[48 + L.n])) + b4g);
 #pragma unroll
       for (int c = 0; c < 4; ++c) y[c] = (y[c] + f[c] * dt) + gs * (z[c] * sq);
+      m_state = fmaxf(m_state, absmax4(y));
       opnd_write(Yop, y, w, L);                            // (its readers of this iteration passed two barriers ago)
       if (live) {
         *reinterpret_cast<f4*>(states + (k + 1) * slab + int64_t(row) * D + ch) = y;
         if (w == 0 && L.g == 0) GS[int64_t(k) * N + row] = gs;
       }
     }
+    range_note(m_state, RS_DEC_STATE);
   }
 }
 
