@@ -271,7 +271,11 @@ int trajsde_encoder_forward(const trajsde_batch* b, const trajsde_graph* g, cons
 /* ---- LocalEncoderSDESepPara2.forward_ood (ENC:204-370): graph prepared with b->A = 0 (no fake agents);
  *      n_samples (reference: 10) stochastic recurrences from a zero state; stds[n] = std over samples of
  *      the kept latent state (unbiased), averaged over the 64 channels; local_embed from the sample mean.
- *      Noise layout when injected: z [n_samples*H, N, 64]; Philox step index = sample*H + iteration. */
+ *      Noise layout when injected: z [n_samples*H, N, 64]; Philox step index = sample*H + iteration.
+ *      The graph may come from trajsde_graph_prepare or, like trajsde_encoder_forward's, from trajsde_graph_prepare_async (list
+ *      lengths on the device; needs the fused edge attention, trajsde_sync_free_supported()): trajsde_encoder_ood_ws_bytes then
+ *      returns the bound-sized figure, the call neither waits for the GPU nor allocates, and with noise->seed_dev it can be
+ *      captured in a hipGraph.  Same outputs bit for bit on either graph. */
 int64_t trajsde_encoder_ood_ws_bytes(const trajsde_batch* b, const trajsde_graph* g, int n_samples);
 int trajsde_encoder_forward_ood(const trajsde_batch* b, const trajsde_graph* g, const float* rotate_mat,
                                 const float* blob, const float* enc_step_table /*HOST memory, [H,8]*/,
@@ -328,7 +332,12 @@ int trajsde_decoder_forward_milstein(int32_t N, int num_modes, int future_steps,
 
 /* ---- vanilla HiVT variant (configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml): LocalEncoder.forward
  *      (enc_hivt_nusargo_grid.py:52-93: AAEncoder, TemporalEncoder :225-292, ALEncoder; graph prepared with A = 0) and
- *      MLPDecoder.forward (dec_hivt_nusargo_grid.py:47-63).  Blobs: TRAJSDE_STAGE_ENCODER_GRID / _DECODER_MLP. */
+ *      MLPDecoder.forward (dec_hivt_nusargo_grid.py:47-63).  Blobs: TRAJSDE_STAGE_ENCODER_GRID / _DECODER_MLP.
+ *      trajsde_encoder_grid_forward and _grid_forward_train take the graph of trajsde_graph_prepare or, like
+ *      trajsde_encoder_forward, of trajsde_graph_prepare_async (list lengths on the device; needs the fused edge attention,
+ *      trajsde_sync_free_supported()): trajsde_encoder_grid_ws_bytes then returns the bound-sized figure and the call does not
+ *      wait for the GPU.  Same outputs bit for bit on either graph.
+ *      The backward entry points below keep asking for exact list lengths. */
 int64_t trajsde_encoder_grid_ws_bytes(const trajsde_batch* b, const trajsde_graph* g);
 int trajsde_encoder_grid_forward(const trajsde_batch* b, const trajsde_graph* g, const float* rotate_mat, const float* blob,
                                  int num_heads, int num_temporal_layers, void* ws, int64_t ws_bytes,

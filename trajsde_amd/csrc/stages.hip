@@ -371,7 +371,7 @@ int trajsde_encoder_forward_ood(const trajsde_batch* b, const trajsde_graph* g, 
                                 int64_t ws_bytes, float* local_embed, float* stds, void* stream_) {
   TS_REQUIRE(b && g && rot && blob && step_tab && ws && local_embed && stds, "encoder_forward_ood: null pointer");
   TS_REQUIRE(g->aa_dst && g->la_dst && g->orig, "encoder_forward_ood: graph not compacted");
-  TS_REQUIRE(g->exact, "encoder_forward_ood: needs exact list lengths (trajsde_graph_prepare, not _async)");
+  TS_REQUIRE(g->exact || (attn_fused() && g->counts), "encoder_forward_ood: a graph from trajsde_graph_prepare_async needs the fused edge attention");
   TS_REQUIRE(b->A == 0 && g->Nt == b->N, "encoder_forward_ood: prepare the graph with A = 0 (no fake agents)");
   TS_REQUIRE(n_samples >= 1, "encoder_forward_ood: n_samples < 1");
   if (ws_bytes < trajsde_encoder_ood_ws_bytes(b, g, n_samples)) return fail(TRAJSDE_ERR_WORKSPACE, "encoder_forward_ood: workspace too small");
@@ -417,7 +417,7 @@ int trajsde_encoder_grid_forward_train(const trajsde_batch* b, const trajsde_gra
   const bool dropping = dropout && dropout->p > 0.f;
   auto drop_of = [&](int block) { return dropping ? make_drop(dropout->p, dropout->seed, block) : no_drop(); };
   TS_REQUIRE(g->aa_dst && g->la_dst && g->orig, "encoder_grid_forward: graph not compacted");
-  TS_REQUIRE(g->exact, "encoder_grid_forward: needs exact list lengths (trajsde_graph_prepare, not _async)");
+  TS_REQUIRE(g->exact || (attn_fused() && g->counts), "encoder_grid_forward: a graph from trajsde_graph_prepare_async needs the fused edge attention");
   TS_REQUIRE(b->A == 0 && g->Nt == b->N, "encoder_grid_forward: prepare the graph with A = 0 (no fake agents)");
   TS_REQUIRE(b->H == 21, "encoder_grid_forward: the temporal kernels are built for historical_steps = 21");
   TS_REQUIRE(num_heads == 8 || num_heads == 4, "encoder_grid_forward: num_heads must be 8 or 4");

@@ -4,7 +4,7 @@ Constructor kwargs as in configs/nusargo/hivt_nuSArgo_trmenc_mlpdec.yml:52-60; c
 `decoder(data=..., local_embed=..., global_embed=...) -> {'loc','pi','reg_mask','local_embed','global_embed'}`.
 """
 from trajsde_amd.models.params import ParamTree
-from trajsde_amd import runtime
+from trajsde_amd import runtime, stage_autograd
 
 
 class MLPDecoder(ParamTree):
@@ -17,6 +17,7 @@ class MLPDecoder(ParamTree):
         d, t = self.hidden_size, self.future_steps
         if d != 64 or self.input_size != 64 or not 0 < t <= 64:
             raise NotImplementedError("kernels are specialised for 64 channels, future_steps <= 64")
+        stage_autograd.check_decoder(self)                       # `autograd: true`: the scale head is needed
         self.linear("aggr_embed.0", d, self.input_size + d)
         self.layernorm("aggr_embed.1", d)
         self.head("loc", d, d, 2 * t)
@@ -34,4 +35,8 @@ class MLPDecoder(ParamTree):
         self._rt = runtime.StageRuntime(self, "decoder_mlp")
 
     def forward(self, data, local_embed, global_embed):
+        """With `autograd: true` among the kwargs, and an input or a parameter requiring grad while grad mode is on, `loc` and `pi` come
+        from the stage's autograd node (stage_autograd.MLPDecoderNode), whose backward is trajsde_mlp_decoder_cotangent_backward"""
+        if stage_autograd.active(self, local_embed, global_embed):
+            return stage_autograd.decoder_mlp(self, data, local_embed, global_embed)
         return self._rt.mlp_decoder_forward(data, local_embed, global_embed)

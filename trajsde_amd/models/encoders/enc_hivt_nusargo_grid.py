@@ -8,7 +8,7 @@ All arithmetic runs in the HIP kernels (csrc/attn.hip, csrc/grid.hip); there is 
 import torch
 
 from trajsde_amd.models.params import ParamTree
-from trajsde_amd import runtime
+from trajsde_amd import runtime, stage_autograd
 
 
 class LocalEncoder(ParamTree):
@@ -52,6 +52,12 @@ class LocalEncoder(ParamTree):
         self.set_init_seed(None)
         self._rt = runtime.StageRuntime(self, "encoder_grid")
 
-    def forward(self, data, noise=None):
-        """`noise` (ours): the NoiseSpec whose key the train-mode dropout masks are cut from (csrc/dropout.hpp); eval mode needs none"""
-        return self._rt.encoder_grid_forward(data, noise)
+    def forward(self, data, noise=None, exact_graph: bool = False):
+        """`noise` (ours): the NoiseSpec whose key the train-mode dropout masks are cut from (csrc/dropout.hpp); eval mode needs none.
+        `exact_graph` (ours): the forward of a training step -- the graph is built with its list lengths on the host, which the
+        backward entry points need; an inference forward leaves them on the device and never waits for the GPU.
+        With `autograd: true` among the kwargs, and a parameter that requires grad while grad mode is on, `local_embed` comes from the
+        stage's autograd node (stage_autograd.GridEncoderNode)"""
+        if stage_autograd.active(self):
+            return stage_autograd.encoder_grid(self, data, noise)
+        return self._rt.encoder_grid_forward(data, noise, exact=exact_graph)

@@ -30,7 +30,7 @@ class _GridLoss(torch.autograd.Function):
     def forward(ctx, model, data, noise, *params):
         with torch.no_grad():
             custom = model._cotangent_route()
-            out = model(data, noise=noise)
+            out = model(data, noise=noise, exact_graph=True)
             local, glob = out["local_embed"], out["global_embed"]
             dec_rt = model.decoder._rt
             if custom:
@@ -64,15 +64,17 @@ class _GridLoss(torch.autograd.Function):
 
 
 class PredictionModel(GlueBase):
-    def forward(self, data, noise: Optional["runtime.NoiseSpec"] = None):
+    def forward(self, data, noise: Optional["runtime.NoiseSpec"] = None, exact_graph: bool = False):
         """models/model_base_mix.py:74-92.  `noise` (optional, ours): the key of the train-mode dropout masks; the default draws a fresh
-        one from torch's global generator, like the reference's dropout draws fresh masks.  Eval mode uses no randomness."""
+        one from torch's global generator, like the reference's dropout draws fresh masks.  Eval mode uses no randomness.
+        `exact_graph` (ours): set by `training_step`, whose backward needs the graph's list lengths on the host; any other forward
+        leaves them on the device (runtime.sync_free) and does not wait for the GPU."""
         if self.training:
             noise = runtime.NoiseSpec.resolve(noise)
         if not self.rotate:
             raise NotImplementedError("rotate=False is not built (shipped config: rotate: true)")
         self._ensure_rotated(data)
-        local_embed = self.encoder(data=data, noise=noise)
+        local_embed = self.encoder(data=data, noise=noise, **({"exact_graph": True} if exact_graph else {}))
         global_embed = self.aggregator(data=data, local_embed=local_embed, noise=noise)
         return self.decoder(data=data, local_embed=local_embed, global_embed=global_embed)
 

@@ -83,6 +83,10 @@ class GraphedForward:
     sized from bounds) and the Philox key can live in device memory (NoiseSpec.seed_dev): a replay re-runs graph preparation,
     encoder, global interactor and decoder on whatever the batch tensors hold NOW, with the key written before the replay.
     The batch tensors must keep their shapes and addresses (update them in place); outputs are the captured tensors.
+    `model`: the SDE model, also with `model.ood = True` (the key seeds the `n_samples` recurrences, the outputs include `stds`).
+    The vanilla HiVT PredictionModel is refused: its forward is sync-free and was captured and replayed bit for bit at small shapes,
+    but ten back-to-back replays at 64 x 128 agents ended in the look-back guard of the graph stage's prefix sum (prep.hip
+    lookback_prefix: a predecessor's word read as never published) and the cause is not found -- DESIGN.md section 7.
 
         gf = GraphedForward(model, batch)          # warm-up + capture
         out = gf(seed=123)                         # one graph launch; out["loc"] etc. are overwritten by the next call
@@ -95,6 +99,11 @@ class GraphedForward:
             raise _lib.TrajsdeError("GraphedForward needs the sync-free forward (TRAJSDE_SYNC_FREE, default kernel forms)")
         if model.training:
             raise _lib.TrajsdeError("GraphedForward captures the inference forward: call model.eval() first")
+        enc_rt = getattr(getattr(model, "encoder", None), "_rt", None)
+        if enc_rt is not None and enc_rt.stage == "encoder_grid":
+            raise _lib.TrajsdeError("GraphedForward does not capture the vanilla HiVT model: replays of its graph at 64 x 128 agents ended "
+                                    "in the graph stage's look-back guard and the cause is not found (DESIGN.md section 7); its eager "
+                                    "forward is sync-free")
         self.model, self.data = model, data
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=x.device)
         self.noise = NoiseSpec(seed=0, seed_dev=self.seed_dev)
@@ -119,6 +128,8 @@ class GraphedForward:
         with torch.cuda.graph(self.graph, stream=cap), torch.no_grad():
             data.y = self._y
             self.out = model(data, noise=self.noise)
+        if GraphContext.KEY in data:                                         # its lists live in the capture's pool and hold nothing before the
+            del data[GraphContext.KEY]                                       # first replay: an eager forward of this batch builds its own
 
     def __call__(self, seed: int):
         self.seed_dev.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
@@ -980,7 +991,7 @@ class StageRuntime:
         """LocalEncoderSDESepPara2.forward_ood (ENC:204-370) -> (local_embed, actors_std)."""
         m = self.module
         noise = NoiseSpec.resolve(noise)
-        gc = GraphContext.get(data, float(m.local_radius), int(m.historical_steps), noise, fake_agents=False)
+        gc = GraphContext.get(data, float(m.local_radius), int(m.historical_steps), noise, fake_agents=False, exact=not sync_free())
         dev = gc.device
         L = _lib.lib()
         blob = self.blob()
@@ -1076,14 +1087,17 @@ class StageRuntime:
         return RelPrefetch(gc, ws, ws_bytes, done, dev)
 
     # ---------------------------------------------------------------- vanilla HiVT variant
-    def encoder_grid_forward(self, data, noise: Optional[NoiseSpec] = None) -> torch.Tensor:
+    def encoder_grid_forward(self, data, noise: Optional[NoiseSpec] = None, exact: bool = False) -> torch.Tensor:
         """LocalEncoder.forward (enc_hivt_nusargo_grid.py:52-93) -> local_embed [N,64].  In train mode the module's `dropout` is
-        applied at the reference's sites with masks keyed by `noise` (csrc/dropout.hpp); the variant draws no other noise."""
+        applied at the reference's sites with masks keyed by `noise` (csrc/dropout.hpp); the variant draws no other noise.
+        `exact`: the caller is a training forward (training_step, a stage autograd node) whose backward needs the list lengths on the
+        host anyway -- the graph is built exact; otherwise it is built sync-free (lengths on the device) like encoder_forward's."""
         m = self.module
         dr = noise.c_dropout(m) if noise is not None else None
         if dr is None and m.training and float(getattr(m, "dropout", 0.0) or 0.0) > 0:
             raise _lib.TrajsdeError("encoder_grid_forward in train mode needs a NoiseSpec (dropout key)")
-        gc = GraphContext.get(data, float(m.local_radius), int(m.historical_steps), NoiseSpec(seed=0), fake_agents=False)   # no fake agents: the graph only
+        gc = GraphContext.get(data, float(m.local_radius), int(m.historical_steps), NoiseSpec(seed=0), fake_agents=False,   # no fake agents: the graph only
+                              exact=True if exact else not sync_free())
         dev = gc.device
         L = _lib.lib()
         blob = self.blob()
@@ -1423,8 +1437,8 @@ class GraphContext:
     @classmethod
     def get(cls, data, radius: Optional[float], H: int, noise: Optional[NoiseSpec], fake_agents: bool = True,
             want_senders: bool = False, exact: Optional[bool] = True, sync_free_cap: Optional[int] = None) -> "GraphContext":
-        """`exact`: True -- the caller's entry point needs the list lengths on the host (training, backward, OOD, vanilla
-        variant, captures); False -- build sync-free if a build is needed; None -- take whatever the encoder left."""
+        """`exact`: True -- the caller's entry point needs the list lengths on the host (training, backward, captures of
+        intermediates); False -- build sync-free if a build is needed; None -- take whatever the encoder left."""
         gc = data[cls.KEY] if cls.KEY in data else None
         if gc is not None and want_senders and not gc.graph.aa_src and gc.graph.E_aa > 0:
             gc = None                                                     # built without the sender ids: rebuild

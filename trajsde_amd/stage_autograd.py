@@ -1,4 +1,4 @@
-"""The three stages of the SDE model as torch.autograd nodes (`autograd: true` among a stage's kwargs).
+"""The stages of the SDE model and of the vanilla HiVT variant as torch.autograd nodes (`autograd: true` among a stage's kwargs).
 
 A stage's `forward` normally runs the inference kernels and returns tensors without a `grad_fn`; training then needs the model-level
 `training_step` (models/model_base_mix_sde.py), one node over the three HIP backward entry points.  With the switch on, a stage whose
@@ -8,8 +8,13 @@ parameters or tensor inputs require grad (and while grad mode is enabled) goes t
     aggregator   aggregator_forward_train    / trajsde_aggregator_backward_heads    (cotangent of global_embed -> d local_embed)
     decoder      decoder_forward             / trajsde_decoder_cotangent_backward(_sel)  (cotangents of loc, pi -> d local / d global)
 
-so a glue module other than ours -- the reference's own PredictionModelSDENet with three `file_path` strings pointed here -- trains
-under any torch loss on any of the outputs.  A node's inputs are the stage's tensor inputs and its parameters in named_parameters()
+and, in the vanilla HiVT variant (LocalEncoder / GlobalInteractor / MLPDecoder; the aggregator's node is the one above, at 4 heads),
+
+    encoder      encoder_grid_forward on the exact graph / trajsde_encoder_grid_backward_train   (cotangent of local_embed)
+    decoder      mlp_decoder_forward         / trajsde_mlp_decoder_cotangent_backward    (cotangents of loc, pi -> d local / d global)
+
+so a glue module other than ours -- the reference's own PredictionModelSDENet or PredictionModel with three `file_path` strings pointed
+here -- trains under any torch loss on any of the outputs.  A node's inputs are the stage's tensor inputs and its parameters in named_parameters()
 order; its backward returns one gradient per parameter, None where the stage's *_BWD table does not name it.  The noise (and the
 dropout key in train mode) is resolved once in forward and replayed by backward; tapes live on the node and are released by backward.
 Every other case -- the switch off, no_grad / inference_mode, nothing requiring grad -- takes the inference path untouched.
@@ -144,6 +149,47 @@ class DecoderNode(torch.autograd.Function):
             + _param_grads(ctx, res["grads"])
 
 
+class GridEncoderNode(torch.autograd.Function):
+    """the vanilla LocalEncoder.forward -> local_embed [N,64]; no tape: the backward entry point recomputes the forward under the
+    node's dropout key"""
+
+    @staticmethod
+    def forward(ctx, module, data, noise, names, *params):
+        _begin(ctx, module, data, noise, names, 0)
+        local = module._rt.encoder_grid_forward(data, noise, exact=True)
+        ctx.save_for_backward(*params)
+        return local
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_local):
+        ctx.saved_tensors                                # torch's version check (see EncoderNode)
+        _replay_guard(ctx)
+        res = ctx.module._rt.encoder_grid_backward(ctx.data, d_local, ctx.noise)
+        return (None, None, None, None) + _param_grads(ctx, res["grads"])
+
+
+class MLPDecoderNode(torch.autograd.Function):
+    """MLPDecoder.forward: (local_embed, global_embed) -> (loc [K,N,T,4], pi [N,K], reg_mask); all K modes and the pi head"""
+
+    @staticmethod
+    def forward(ctx, module, data, noise, names, local_embed, global_embed, *params):
+        _begin(ctx, module, data, noise, names, 2)
+        out = module._rt.mlp_decoder_forward(data, local_embed, global_embed)
+        ctx.save_for_backward(local_embed, global_embed, out["loc"], *params)
+        ctx.mark_non_differentiable(out["reg_mask"])
+        return out["loc"], out["pi"], out["reg_mask"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loc, d_pi, _d_mask):
+        local_embed, global_embed, loc = ctx.saved_tensors[:3]
+        res = ctx.module._rt.mlp_decoder_cotangent_backward(ctx.data, local_embed, global_embed, {"loc": loc}, d_loc, d_pi)
+        need = ctx.needs_input_grad
+        return (None, None, None, None, res["d_local_embed"] if need[4] else None, res["d_global_embed"] if need[5] else None) \
+            + _param_grads(ctx, res["grads"])
+
+
 def _enter(module, noise: Optional["runtime.NoiseSpec"]):
     names, params = _params(module)
     return runtime.NoiseSpec.resolve(noise), names, params
@@ -172,3 +218,18 @@ def decoder(module, data, local_embed, global_embed, noise=None):
     runtime._require_gpu(global_embed, "global_embed")
     loc, pi, reg_mask = DecoderNode.apply(module, data, noise, names, local_embed, global_embed, *params)
     return {"loc": loc, "pi": pi, "reg_mask": reg_mask}
+
+
+def encoder_grid(module, data, noise=None):
+    noise, names, params = _enter(module, noise)
+    return GridEncoderNode.apply(module, data, noise, names, *params)
+
+
+def decoder_mlp(module, data, local_embed, global_embed):
+    """the dict of MLPDecoder.forward (dec_hivt_nusargo_grid.py:56-57: the embeddings ride along, here with their own history)"""
+    check_decoder(module)
+    names, params = _params(module)                                     # (the stage draws nothing: no key to resolve)
+    runtime._require_gpu(local_embed, "local_embed")
+    runtime._require_gpu(global_embed, "global_embed")
+    loc, pi, reg_mask = MLPDecoderNode.apply(module, data, None, names, local_embed, global_embed, *params)
+    return {"loc": loc, "pi": pi, "reg_mask": reg_mask, "local_embed": local_embed, "global_embed": global_embed}
