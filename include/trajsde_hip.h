@@ -220,7 +220,8 @@ typedef struct {
   const int32_t* la_lane;     /* [E_la] lane segment; null unless trajsde_export_senders(1)                      */
   /* ABI 5: the three list lengths on the DEVICE (counts[1] = E_aa, [2] = E_g, [3] = E_la).  With exact = 0
    * (trajsde_graph_prepare_async) the E_* fields above are UPPER BOUNDS that size buffers and grids, the kernels of the
-   * inference forward read the true lengths here, and no host synchronisation happens anywhere in the forward. */
+   * inference forward read the true lengths here, and no host synchronisation happens anywhere in the forward.
+   * counts[6] = 1 when the actor CSR was written from the closed form of a dataset-order edge list, 0 when it was sorted. */
   const int32_t* counts;
   int32_t exact;              /* 1: E_aa / E_g / E_la are the true lengths (trajsde_graph_prepare) */
 } trajsde_graph;

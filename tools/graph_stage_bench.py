@@ -20,9 +20,19 @@ def main():
     ap.add_argument("--workload", default="metric256")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--exact", action="store_true")
+    ap.add_argument("--edges", default="dataset", choices=("dataset", "shuffled", "swapped"),
+                    help="the actor edge list as the datasets emit it, randomly permuted, or with ONE pair of neighbouring edges exchanged "
+                         "(the last two are the same graph, not in dataset order: the device-decided general path, caught early / late)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    batch = synth(**CONFIGS[a.workload]["synth"]).to(dev)
+    batch = synth(**CONFIGS[a.workload]["synth"])
+    ei = batch["edge_index"]
+    if a.edges == "shuffled":
+        batch["edge_index"] = ei[:, torch.randperm(ei.shape[1], generator=torch.Generator().manual_seed(1))].contiguous()
+    elif a.edges == "swapped":
+        j = ei.shape[1] // 2
+        ei[:, [j, j + 1]] = ei[:, [j + 1, j]]
+    batch = batch.to(dev)
     rot, y_rot = runtime.rotate_inputs(batch)
     batch["rotate_mat"] = rot
 
@@ -39,7 +49,8 @@ def main():
         gc = once(10 + i)
     e1.record()
     torch.cuda.synchronize()
-    print(f"graph stage ({'exact' if a.exact else 'sync-free'}): {e0.elapsed_time(e1) / a.iters * 1e3:.1f} us per batch, counts {gc.true_counts()}")
+    print(f"graph stage ({'exact' if a.exact else 'sync-free'}, {a.edges} edge order): {e0.elapsed_time(e1) / a.iters * 1e3:.1f} us per batch, counts {gc.true_counts()}, "
+          f"actor CSR path: {gc.graph_path()}")
     _lib.lib().trajsde_profile_mode(2)
     for i in range(3):
         once(1000 + i)

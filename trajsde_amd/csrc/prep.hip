@@ -55,6 +55,25 @@ __global__ void k_rotate(const float* __restrict__ ang, int N, const float* __re
 //                 last derives the segment pointers of the global / lane lists and the list lengths
 //   k_graph_fill  trajsde_graph_compact: block ranges -- the agent-agent snapshot records, the global list, the lane list
 // Every result is bit for bit what the 22-launch form produced (integer work; the geometry expressions are the same).
+//
+// The actor CSR without the sort.  The datasets emit the actor edge list per scene as permutations(range(n), 2) and
+// collation concatenates the scenes with node offsets: source-major and complete per scene ("dataset order").  A complete graph is its
+// own transpose, so row t of the target-major CSR is "every other node of t's scene, ascending" and the row pointers follow from the
+// scene extents alone -- no histogram, no scatter, no row sort.  The stage ASSUMES that order and CHECKS it on the device:
+//   k_prep_first  instead of the actor histogram: in-degree of node i = (size of i's scene) - 1 from a binary search in `batch`, the
+//                 scene's first node (scene_lo), and the check that `batch` is non-decreasing
+//   k_direct2     instead of the actor half of k_scatter2: every position p of the INPUT list is compared with the closed form (its source s
+//                 is the row with rowptr[s] <= p < rowptr[s+1], its target lo + k + (lo + k >= s), k = p - rowptr[s]); the row pointers
+//                 must ascend to E; csr_src / csr_dst / flags_g are written in the same pass -- optimistically
+//   k_aa_count, k_graph_fill   on this path a row's candidate idx is node lo + idx + (lo + idx >= o): no csr_src gather at the head of
+//                 their dependent chains
+//   any mismatch raises ONE word of the zeroed block (PrepWs::general, non-returning atomic).  The general path follows as launches that
+//   return at their first instruction while the word is zero: k_fb_degree (histogram + row pointers), k_fb_scatter, and the actor
+//   blocks of k_row_sort2 -- they write over everything the optimistic pass left.  Nothing waits for the word inside a launch: it is
+//   raised by whole earlier launches and read by later ones of the same stream.
+// A list that is not in dataset order pays for the attempt: the general path as three launches of its own plus the first two -- measured
+// in profiles/r07_ab_runs.md.  TRAJSDE_GRAPH_DIRECT=0 (or E == 0) takes the general path on the host: exactly the six launches above,
+// for callers whose lists are never in dataset order.
 
 // "the workgroup that finishes last continues": every workgroup waits until its own writes have been performed, takes a number, and
 // the one that draws the last number reads what the others left.  NO device-wide fence: on this chip an agent-scope release is a
@@ -431,6 +450,7 @@ __device__ __forceinline__ void lane_feat_body(int l, int L, int P, const float*
 // exclusive prefix sums of TWO count arrays of n entries by one workgroup of 256 threads (the row pointers of the two CSRs: n = N + 1),
 // 8 192 entries per round -- 32 consecutive entries per thread, all requested before the first is used; the counts were formed by other
 // workgroups' atomics: read coherently
+template <int NA = 2>
 __device__ __forceinline__ void block_scan_two(const int32_t* __restrict__ in0, int32_t* __restrict__ out0, const int32_t* __restrict__ in1,
                                                int32_t* __restrict__ out1, int n) {
   __shared__ int32_t s_w[2][4];
@@ -439,30 +459,40 @@ __device__ __forceinline__ void block_scan_two(const int32_t* __restrict__ in0, 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   if (t < 2) s_carry[t] = 0;
   __syncthreads();
-  const CoherentI32 c0(in0), c1(in1);
+  const CoherentI32 c0(in0), c1(NA > 1 ? in1 : in0);
   for (int base = 0; base < n; base += 256 * PT) {
-    int32_t v[2][PT], sum[2] = {0, 0};
+    int32_t v[NA][PT], sum[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) sum[a] = 0;
 #pragma unroll
     for (int c = 0; c < PT; ++c) {
       const int i = base + PT * t + c;
       v[0][c] = i < n ? c0[i] : 0;
-      v[1][c] = i < n ? c1[i] : 0;
+      if constexpr (NA > 1) v[1][c] = i < n ? c1[i] : 0;
     }
 #pragma unroll
     for (int c = 0; c < PT; ++c) {
-      sum[0] += v[0][c];
-      sum[1] += v[1][c];
+#pragma unroll
+      for (int a = 0; a < NA; ++a) sum[a] += v[a][c];
     }
-    int32_t inc[2] = {sum[0], sum[1]};
+    int32_t inc[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) inc[a] = sum[a];
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-      const int32_t o0 = __shfl_up(inc[0], d), o1 = __shfl_up(inc[1], d);
-      if (lane >= d) { inc[0] += o0; inc[1] += o1; }
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const int32_t o = __shfl_up(inc[a], d);
+        if (lane >= d) inc[a] += o;
+      }
     }
-    if (lane == 63) { s_w[0][wv] = inc[0]; s_w[1][wv] = inc[1]; }
+    if (lane == 63) {
+#pragma unroll
+      for (int a = 0; a < NA; ++a) s_w[a][wv] = inc[a];
+    }
     __syncthreads();
 #pragma unroll
-    for (int a = 0; a < 2; ++a) {
+    for (int a = 0; a < NA; ++a) {
       int32_t run = s_carry[a] + inc[a] - sum[a];
       for (int w = 0; w < wv; ++w) run += s_w[a][w];
       int32_t* out = a ? out1 : out0;
@@ -474,13 +504,48 @@ __device__ __forceinline__ void block_scan_two(const int32_t* __restrict__ in0, 
       }
     }
     __syncthreads();
-    if (t < 2) s_carry[t] += s_w[t][0] + s_w[t][1] + s_w[t][2] + s_w[t][3];
+    if (t < NA) s_carry[t] += s_w[t][0] + s_w[t][1] + s_w[t][2] + s_w[t][3];
     __syncthreads();
   }
 }
 
+// ---- dataset-order actor lists: degrees from the scene extents (see the head of this section)
+__device__ __forceinline__ void raise_general(unsigned int* general) {
+  __hip_atomic_fetch_or(general, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (result unused: no return trip)
+}
+// node i: its scene is [first, last) = the run of batch[i] around i (both binary searches in flight together; were `batch` not sorted
+// the answers are still first <= i < last <= N, and the order check below sends the batch down the general path)
+// Each node also looks at ONE pair of neighbouring list positions (a scattered one): in dataset order the sources never descend and the
+// targets of one source ascend.  That proves nothing, but a shuffled, target-major or otherwise reordered list fails it somewhere with
+// near certainty, and then the word is up before k_direct2 starts, whose checking blocks stand down: such a list pays the general path
+// and two near-empty launches, not a discarded pass over the list as well.  `pre_raise`: the A/B switch that sends every batch that way.
+__device__ __forceinline__ void direct_degree_body(int i, int N, const int64_t* __restrict__ batch, const int64_t* __restrict__ ei, int E,
+                                                   int pre_raise, int32_t* __restrict__ deg, int32_t* __restrict__ scene_lo,
+                                                   unsigned int* __restrict__ general) {
+  if (i >= N) return;
+  const int64_t c = batch[i];
+  bool descends = i + 1 < N && batch[i + 1] < c;
+  if (E >= 2) {
+    const int p = int((uint32_t(i) * 2654435761u) % uint32_t(E - 1));
+    const int64_t s0 = ei[p], s1 = ei[p + 1], d0 = ei[int64_t(E) + p], d1 = ei[int64_t(E) + p + 1];
+    descends |= s1 < s0 || (s1 == s0 && d1 <= d0);
+  }
+  descends |= pre_raise != 0 && i == 0;
+  int l0 = 0, h0 = i;                    // first index of [0, i] whose scene id is >= c
+  int l1 = i + 1, h1 = N;                // first index of (i, N] whose scene id is > c (N: none)
+  while (l0 < h0 || l1 < h1) {
+    const int m0 = (l0 + h0) >> 1, m1 = l1 < h1 ? (l1 + h1) >> 1 : i;
+    const int64_t b0 = batch[m0], b1 = batch[m1];
+    if (l0 < h0) { if (b0 < c) l0 = m0 + 1; else h0 = m0; }
+    if (l1 < h1) { if (b1 <= c) l1 = m1 + 1; else h1 = m1; }
+  }
+  store_through(&deg[i], l1 - l0 - 1);   // (read by the launch's last workgroup: block_scan_two)
+  scene_lo[i] = l0;
+  if (descends) raise_general(general);
+}
+
 // First launch of the graph stage: every per-input pass that depends on nothing but the batch, as block ranges of one launch --
-// [0, b0) actor-edge degrees, [b0, b1) lane-edge degrees, [b1, b2) extended-node table, [b2, b3) fake agents' inputs, [b3, b4) validity
+// [0, b0) actor-edge degrees (histogram, or from the scene extents: direct_degree_body), [b0, b1) lane-edge degrees, [b1, b2) extended-node table, [b2, b3) fake agents' inputs, [b3, b4) validity
 // masks, [b4, b5) time-major copies, [b5, ..) lane features -- and, by the workgroup that finishes last, both CSR row pointers
 // (exclusive scans of the degree histograms, which are formed by agent-scope atomics: see last_block_done).
 struct FirstPassArgs {
@@ -494,11 +559,17 @@ struct FirstPassArgs {
   float2 *pos_t, *x_t;
   uint32_t* vmask;
   unsigned int* done;
+  int direct;                    // [0, b0) are direct_degree_body blocks (dataset-order attempt) instead of the actor histogram; 2: word pre-raised
+  int32_t* scene_lo;
+  unsigned int* general;
   NoiseArg na;
 };
 __global__ __launch_bounds__(256) void k_prep_first(const FirstPassArgs a) {
   const int blk = blockIdx.x, i = threadIdx.x;
-  if (blk < a.b0) degree_body(blk, a.edge_index, a.E, a.deg);
+  if (blk < a.b0) {
+    if (a.direct) direct_degree_body(blk * 256 + i, a.N, a.batch, a.edge_index, a.E, a.direct == 2, a.deg, a.scene_lo, a.general);
+    else degree_body(blk, a.edge_index, a.E, a.deg);
+  }
   else if (blk < a.b1) degree_body(blk - a.b0, a.lane_actor_index, a.Ea, a.la_deg);
   else if (blk < a.b2) ext_nodes_body((blk - a.b1) * 256 + i, a.N, a.A, a.H, a.agent_index, a.batch, a.source, a.bos, a.orig, a.nus, a.eos, a.pick_slot);
   else if (blk < a.b3) fake_x_body((blk - a.b2) * 256 + i, a.A, a.H, a.x, a.agent_index, a.na, a.x_fake);
@@ -509,11 +580,88 @@ __global__ __launch_bounds__(256) void k_prep_first(const FirstPassArgs a) {
   block_scan_two(a.deg, a.rowptr, a.la_deg, a.la_rowptr, a.N + 1);
 }
 
+// Second launch of a dataset-order attempt: blocks [0, nb_e) check the input list against the closed form, one thread per POSITION of
+// the list (any mix of scene sizes keeps every lane busy; both rows are coalesced 8-byte reads, four per thread in flight), and write
+// the CSR entry, its target and the global-interactor keep-flag as k_row_sort2 would have; the last blocks are the lane half of
+// k_scatter2.  The source the list names
+// must be the row whose stretch [rowptr[s], rowptr[s + 1]) holds the position -- those stretches tile [0, E) once the row pointers
+// ascend from 0 to E, which blocks [nb_e, nb_e + nb_n) check while they reset the degree counters for the general path -- and the
+// target must be the closed form's.  Ids read from the list index memory only after they are known to be node ids.
+constexpr int DIRECT_EPT = 4;
+__global__ __launch_bounds__(256) void k_direct2(const int64_t* __restrict__ ei, int E, int N, const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ scene_lo, int32_t* __restrict__ deg, const uint32_t* __restrict__ vmask,
+                                                      int tref, int32_t* __restrict__ csr_src, int32_t* __restrict__ csr_dst, uint8_t* __restrict__ flags_g,
+                                                      unsigned int* __restrict__ general, int nb_e, int nb_n, const int64_t* __restrict__ lai, int Ea,
+                                                      const int32_t* __restrict__ la_rowptr, int32_t* __restrict__ la_deg, int64_t* __restrict__ la_pack) {
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  if (blk >= nb_e + nb_n) {
+    scatter_lane_body(blk - nb_e - nb_n, lai, Ea, la_rowptr, la_deg, la_pack);
+    return;
+  }
+  bool bad = false;
+  if (blk >= nb_e) {
+    const int i = (blk - nb_e) * 256 + tid;
+    if (i < N) {
+      deg[i] = 0;                                                          // the general path's histogram counts from zero
+      bad = rowptr[i] > rowptr[i + 1] || (i == N - 1 && rowptr[N] != E);
+    }
+  } else {
+    if (*general != 0u) return;                                            // already known not to be in dataset order (earlier launch)
+    int64_t src[DIRECT_EPT], dst[DIRECT_EPT];
+#pragma unroll
+    for (int u = 0; u < DIRECT_EPT; ++u) {
+      const int p = (blk * DIRECT_EPT + u) * 256 + tid;
+      src[u] = p < E ? ei[p] : -1;
+      dst[u] = p < E ? ei[int64_t(E) + p] : -1;
+    }
+    int beg[DIRECT_EPT], end[DIRECT_EPT], lo[DIRECT_EPT];
+    uint32_t vs[DIRECT_EPT], vd[DIRECT_EPT];
+#pragma unroll
+    for (int u = 0; u < DIRECT_EPT; ++u) {
+      const bool ids = src[u] >= 0 && src[u] < N && dst[u] >= 0 && dst[u] < N;
+      const int sn = ids ? int(src[u]) : 0, dn = ids ? int(dst[u]) : 0;
+      beg[u] = rowptr[sn]; end[u] = rowptr[sn + 1]; lo[u] = scene_lo[sn];
+      vs[u] = vmask[sn]; vd[u] = vmask[dn];
+      if (!ids) beg[u] = INT32_MAX;                                        // (fails the range test below)
+    }
+#pragma unroll
+    for (int u = 0; u < DIRECT_EPT; ++u) {
+      const int p = (blk * DIRECT_EPT + u) * 256 + tid;
+      if (p < E) {
+        const int sn = int(src[u]);
+        const int64_t v = int64_t(lo[u]) + p - beg[u];
+        bad |= !(p >= beg[u] && p < end[u] && dst[u] == v + (v >= sn ? 1 : 0));
+        csr_src[p] = int32_t(dst[u]);
+        csr_dst[p] = sn;
+        flags_g[p] = uint8_t((vs[u] >> tref) & (vd[u] >> tref) & 1u);
+      }
+    }
+  }
+  if (__any(bad) && (tid & 63) == 0) raise_general(general);
+}
+
+// The general path behind a failed dataset-order attempt: the histogram and the row pointers, then the scatter, as launches of their
+// own that return at once while the word is zero (k_row_sort2's actor blocks do the same).  The lane CSR is not touched.
+__global__ __launch_bounds__(256) void k_fb_degree(const unsigned int* __restrict__ general, const int64_t* __restrict__ ei, int E, int N,
+                                                   int32_t* __restrict__ deg, int32_t* __restrict__ rowptr, unsigned int* __restrict__ done) {
+  if (*general == 0u) return;
+  degree_body(blockIdx.x, ei, E, deg);
+  if (!last_block_done(done, gridDim.x)) return;
+  block_scan_two<1>(deg, rowptr, nullptr, nullptr, N + 1);
+}
+__global__ __launch_bounds__(256) void k_fb_scatter(const unsigned int* __restrict__ general, const int64_t* __restrict__ ei, int E,
+                                                    const int32_t* __restrict__ rowptr, int32_t* __restrict__ deg, int32_t* __restrict__ csr_src) {
+  if (*general == 0u) return;
+  scatter_body(blockIdx.x, ei, E, rowptr, deg, csr_src);
+}
+
 // Canonical order of both CSRs in one launch: blocks [0, nb_a) sort the actor rows (values = senders; also names the target of every
 // position, csr_dst, and writes the keep-flag of the global-interactor edge at that position: both ends valid at the reference step,
 // AGG:41), the rest sort the lane rows (values = lane << 32 | edge id; writes the edge ids, the actor of every position and the
 // keep-flag of the lane-actor edge: |vector| < radius, ENC:198).  flags[E] (the scans' extra element) is zero.
-__global__ __launch_bounds__(256) void k_row_sort2(int N, int nb_a, int nb_l, const int32_t* __restrict__ rowptr, int32_t* __restrict__ csr_src,
+// `general`: null, or the word of a dataset-order attempt -- while it is zero the actor rows are already in place (k_direct2) and the
+// actor blocks stand down.
+__global__ __launch_bounds__(256) void k_row_sort2(const unsigned int* __restrict__ general, int N, int nb_a, int nb_l, const int32_t* __restrict__ rowptr, int32_t* __restrict__ csr_src,
                                                    int32_t* __restrict__ csr_dst, const uint32_t* __restrict__ vmask, int tref, int E,
                                                    uint8_t* __restrict__ flags_g, const int32_t* __restrict__ la_rowptr,
                                                    int64_t* __restrict__ la_pack, int32_t* __restrict__ la_eid, int32_t* __restrict__ la_actor,
@@ -526,6 +674,7 @@ __global__ __launch_bounds__(256) void k_row_sort2(int N, int nb_a, int nb_l, co
   }
   if (blk < nb_a) {
     if (E <= 0) return;
+    if (general != nullptr && *general == 0u) return;
     auto emit = [&](int p, int32_t sender, int row) { flags_g[p] = uint8_t((vmask[sender] >> tref) & (vmask[row] >> tref) & 1u); };
     row_sort_part<int32_t>(blk, nb_a, rowptr, N, csr_src, nullptr, csr_dst, reinterpret_cast<int32_t*>(buf), emit);
   } else {
@@ -694,6 +843,8 @@ struct AaArgs {
   int32_t* segptr;
   int32_t* counts;
   unsigned long long* bal;                 // [row chunk][H]; the chunks of row o start at (rowptr[o] >> 6) + o
+  const unsigned int* general;             // the word of a dataset-order attempt (null: none was made); counts[6] reports the path
+  const int32_t* scene_lo;                 // first node of every actor's scene (valid while the word is zero)
   int32_t *aa_dst, *aa_src;
   float* geom;
 };
@@ -709,6 +860,10 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long w, int r) {
   }
   return posn;
 }
+// a direct-path row holds the scene's nodes but its own, ascending: candidate idx of row o is lo + idx + (lo + idx >= o), no csr_src gather
+__device__ __forceinline__ bool aa_direct(const AaArgs& a) {
+  return a.general != nullptr && *a.general == 0u;
+}
 constexpr int AA_CG = 4, AA_SG = 7;        // candidates: 64 x AA_CG in registers; steps: AA_SG loads in flight per chunk
 __global__ __launch_bounds__(256) void k_aa_count(const AaArgs a) {
   const int lane = threadIdx.x & 63;
@@ -720,6 +875,7 @@ __global__ __launch_bounds__(256) void k_aa_count(const AaArgs a) {
     a.segptr[int64_t(H) * Nt] = 0;                                         // the scan's extra element (total at the end)
     reinterpret_cast<float*>(a.counts)[4] = a.radius;
     reinterpret_cast<float*>(a.counts)[5] = a.thr2;                        // the threshold the counts are formed with: the fill reads it here
+    a.counts[6] = a.general != nullptr && *a.general == 0u ? 1 : 0;        // 1: the actor CSR came from the closed form (k_direct2)
   }
   if (node >= Nt) return;
   const int o = node < N ? node : __builtin_amdgcn_readfirstlane(a.orig[node]);
@@ -727,15 +883,25 @@ __global__ __launch_bounds__(256) void k_aa_count(const AaArgs a) {
   const uint32_t vo = __builtin_amdgcn_readfirstlane(a.vmask[o]);
   const int chunks = (end - beg + 63) >> 6;
   const int64_t bbase = bal_base(beg, o);
+  const bool direct = aa_direct(a);                                        // (uniform)
+  const int lo = direct ? __builtin_amdgcn_readfirstlane(a.scene_lo[o]) : 0;
   const float thr2 = a.thr2;
   int mycnt = 0;                                                           // lane t: survivors of (t, node)
   for (int c0 = 0; c0 < chunks; c0 += AA_CG) {
     int s[AA_CG];
     uint32_t m[AA_CG];
+    if (direct) {
 #pragma unroll
-    for (int u = 0; u < AA_CG; ++u) {
-      const int p = beg + 64 * (c0 + u) + lane;
-      s[u] = p < end ? a.csr_src[p] : -1;
+      for (int u = 0; u < AA_CG; ++u) {
+        const int idx = 64 * (c0 + u) + lane, v = lo + idx;
+        s[u] = beg + idx < end ? v + (v >= o ? 1 : 0) : -1;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < AA_CG; ++u) {
+        const int p = beg + 64 * (c0 + u) + lane;
+        s[u] = p < end ? a.csr_src[p] : -1;
+      }
     }
 #pragma unroll
     for (int u = 0; u < AA_CG; ++u) {
@@ -799,6 +965,8 @@ __device__ __forceinline__ void aa_fill_node(const AaArgs& a, int node, int part
     if (lane < nw) w0 = words[lane];
     if (64 + lane < nw) w1 = words[64 + lane];
   }
+  const bool direct = aa_direct(a);                                        // (uniform)
+  const int lo = direct ? __builtin_amdgcn_readfirstlane(a.scene_lo[o]) : 0;
   const f4 R = *reinterpret_cast<const f4*>(a.rot + 4 * o);
   auto word = [&](int c, int t) -> unsigned long long {                    // (uniform arguments, uniform result)
     if (in_regs) {
@@ -830,7 +998,8 @@ __device__ __forceinline__ void aa_fill_node(const AaArgs& a, int node, int part
         if (cum >= r0 + 64) break;                                         // (uniform) every lane of this round is served
       }
       if (r < n) {
-        const int sdr = a.csr_src[beg + 64 * selc + nth_set_bit(selw, rr)];     // senders are real actors
+        const int idx = 64 * selc + nth_set_bit(selw, rr);
+        const int sdr = direct ? lo + idx + (lo + idx >= o ? 1 : 0) : a.csr_src[beg + idx];     // senders are real actors
         const float2 ps = pos_t[sdr], xs = x_t[sdr];
         const float dx = ps.x - pdx, dy = ps.y - pdy;
         const float x0 = xs.x, x1 = xs.y;
@@ -925,6 +1094,9 @@ struct PrepWs {
   float *x_fake, *lane_feat;
   unsigned long long* scan_st;   // SCAN_INSTANCES x SCAN_WORDS zeroed words (k_scan_multi), directly behind the degree counters
   unsigned int* done;            // DONE_WAYS + 1 zeroed "workgroups finished" counters (last_block_done)
+  unsigned int* done_fb;         // the same for k_fb_degree
+  unsigned int* general;         // zeroed word: raised when the actor list is not in dataset order
+  int32_t* scene_lo;             // per actor: first node of its scene (direct_degree_body)
   int64_t zeroed_bytes, n_aa, aa_blocks;
   int64_t total;
   bool ok;
@@ -935,12 +1107,14 @@ struct PrepWs {
     aa_blocks = xcd_grid((Nt * ((H + 6) / 7) + 3) / 4);                    // k_aa_count: one wave per (extended node, group of AA_SG = 7 steps)
     // both degree arrays, the scans' and the look-back's state words, the finish counters: ONE block, one memset (graph_prepare)
     const int64_t deg_ints = (2 * (N + 1) + 1) / 2 * 2;
-    const int64_t st_words = int64_t(SCAN_INSTANCES) * SCAN_WORDS + (DONE_WAYS + 2) / 2 + 1;
+    constexpr int64_t DONE_WORDS = (DONE_WAYS + 2) / 2 + 1;            // 8-byte words per set of finish counters (room to spare)
+    const int64_t st_words = int64_t(SCAN_INSTANCES) * SCAN_WORDS + 2 * DONE_WORDS + 1;
     deg = c.take<int32_t>(deg_ints + 2 * st_words); la_deg = ptr_add(deg, N + 1);
     scan_st = reinterpret_cast<unsigned long long*>(ptr_add(deg, deg_ints));
     done = reinterpret_cast<unsigned int*>(ptr_add(scan_st, int64_t(SCAN_INSTANCES) * SCAN_WORDS));
+    done_fb = done + 2 * DONE_WORDS; general = done_fb + 2 * DONE_WORDS;
     zeroed_bytes = (deg_ints + 2 * st_words) * int64_t(sizeof(int32_t));
-    rowptr = c.take<int32_t>(N + 1);
+    rowptr = c.take<int32_t>(N + 1); scene_lo = c.take<int32_t>(N + 1);
     csr_src = c.take<int32_t>(E + 1); csr_dst = c.take<int32_t>(E + 1);
     orig = c.take<int32_t>(Nt); eos = c.take<int32_t>(Nt); pick_slot = c.take<int32_t>(Nt); counts = c.take<int32_t>(8);
     la_rowptr = c.take<int32_t>(N + 1);
@@ -988,6 +1162,14 @@ static int check_batch(const trajsde_batch* b) {
   return TRAJSDE_OK;
 }
 
+// TRAJSDE_GRAPH_DIRECT (read once): unset / 1 -- attempt the dataset-order path; 0 -- never (the six launches, decided on the host);
+// 2 -- attempt with the word pre-raised, i.e. the device-decided general path on every batch (A/B runs of its cost).  No actor edge: no attempt.
+static int direct_mode(const trajsde_batch* b) {
+  static const int mode = []() { const char* e = getenv("TRAJSDE_GRAPH_DIRECT"); return e && e[0] == '0' && !e[1] ? 0 : (e && e[0] == '2' && !e[1] ? 2 : 1); }();
+  return b->E > 0 ? mode : 0;
+}
+static bool try_direct(const trajsde_batch* b) { return direct_mode(b) != 0; }
+
 static CollectArgs collect_args(const trajsde_batch* b, const PrepWs& w, float radius) {
   CollectArgs c;
   c.n_aa = w.n_aa; c.E = b->E; c.Ea = b->E_al; c.N = b->N;
@@ -1000,7 +1182,8 @@ static AaArgs aa_args(const trajsde_batch* b, const PrepWs& w, const float* rot,
   a.N = b->N; a.Nt = b->N + b->A; a.H = b->H;
   a.radius = radius; a.thr2 = radius2_threshold(radius); a.thr2_dev = 0;
   a.rowptr = w.rowptr; a.csr_src = w.csr_src; a.orig = w.orig; a.vmask = w.vmask; a.pos_t = w.pos_t; a.x_t = w.x_t; a.rot = rot;
-  a.segptr = w.aa_segptr; a.counts = w.counts; a.bal = w.bal;
+  a.segptr = w.aa_segptr; a.counts = w.counts; a.bal = w.bal; a.general = try_direct(b) ? w.general : nullptr;
+  a.scene_lo = w.scene_lo;
   a.aa_dst = nullptr; a.aa_src = nullptr; a.geom = nullptr;
   return a;
 }
@@ -1047,11 +1230,12 @@ static int graph_prepare(const trajsde_batch* b, const float* rot, float radius,
 
   TS_HIP(hipMemsetAsync(w.deg, 0, size_t(w.zeroed_bytes), st));       // degree counters, scan / look-back state words, finish counters
   const int tref = H - 1;
+  const bool direct = try_direct(b);
   {
     ProfScope ps("k_prep_first", st);
     FirstPassArgs fa;
     fa.N = N; fa.A = A; fa.H = H; fa.TT = TT; fa.L = b->L; fa.P = b->lane_pts; fa.E = E; fa.Ea = Ea;
-    fa.b0 = cdiv(E, 256 * EPT);
+    fa.b0 = direct ? cdiv(N, 256) : cdiv(E, 256 * EPT);
     fa.b1 = fa.b0 + cdiv(Ea, 256 * EPT);
     fa.b2 = fa.b1 + cdiv(Nt, 256);
     fa.b3 = fa.b2 + (A > 0 ? cdiv(A * ((2 * H + 3) / 4), 256) : 0);
@@ -1064,9 +1248,25 @@ static int graph_prepare(const trajsde_batch* b, const float* rot, float radius,
     fa.deg = w.deg; fa.la_deg = w.la_deg; fa.rowptr = w.rowptr; fa.la_rowptr = w.la_rowptr; fa.orig = w.orig; fa.eos = w.eos;
     fa.pick_slot = w.pick_slot; fa.nus = w.nus; fa.x_fake = w.x_fake; fa.lane_feat = w.lane_feat; fa.pos_t = w.pos_t; fa.x_t = w.x_t;
     fa.vmask = w.vmask; fa.done = w.done + 0; fa.na = na;
+    fa.direct = direct_mode(b); fa.scene_lo = w.scene_lo; fa.general = w.general;
     k_prep_first<<<fa.blocks, 256, 0, st>>>(fa);
   }
-  if (E > 0 || Ea > 0) {
+  if (direct) {
+    {
+      ProfScope ps("k_direct2", st);
+      const int nb_e = cdiv(E, 256 * DIRECT_EPT), nb_n = cdiv(N, 256);
+      k_direct2<<<nb_e + nb_n + cdiv(Ea, 256 * EPT), 256, 0, st>>>(b->edge_index, E, N, w.rowptr, w.scene_lo, w.deg, w.vmask, tref, w.csr_src, w.csr_dst,
+                                                              w.flags_g, w.general, nb_e, nb_n, b->lane_actor_index, Ea, w.la_rowptr, w.la_deg, w.la_pack);
+    }
+    {
+      ProfScope ps("k_fb_degree", st);
+      k_fb_degree<<<cdiv(E, 256 * EPT), 256, 0, st>>>(w.general, b->edge_index, E, N, w.deg, w.rowptr, w.done_fb);
+    }
+    {
+      ProfScope ps("k_fb_scatter", st);
+      k_fb_scatter<<<cdiv(E, 256 * EPT), 256, 0, st>>>(w.general, b->edge_index, E, w.rowptr, w.deg, w.csr_src);
+    }
+  } else if (E > 0 || Ea > 0) {
     ProfScope ps("k_scatter2", st);
     const int nb_a = cdiv(E, 256 * EPT);
     k_scatter2<<<nb_a + cdiv(Ea, 256 * EPT), 256, 0, st>>>(b->edge_index, E, w.rowptr, w.deg, w.csr_src, nb_a, b->lane_actor_index, Ea, w.la_rowptr,
@@ -1075,7 +1275,7 @@ static int graph_prepare(const trajsde_batch* b, const float* rot, float radius,
   {
     ProfScope ps("k_row_sort2", st);
     const int per_list = cdiv(N, 4) < 8192 ? cdiv(N, 4) : 8192;
-    k_row_sort2<<<2 * per_list, 256, 0, st>>>(N, per_list, per_list, w.rowptr, w.csr_src, w.csr_dst, w.vmask, tref, E, w.flags_g, w.la_rowptr,
+    k_row_sort2<<<2 * per_list, 256, 0, st>>>(direct ? w.general : nullptr, N, per_list, per_list, w.rowptr, w.csr_src, w.csr_dst, w.vmask, tref, E, w.flags_g, w.la_rowptr,
                                               w.la_pack, w.la_eid, w.la_actor, b->lane_actor_vectors, radius, Ea, w.flags_la);
   }
   {

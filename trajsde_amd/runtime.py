@@ -1392,6 +1392,18 @@ class GraphContext:
             c = self._i32(self.ws, g.counts, 4).tolist()
         return {"E_aa": c[1], "E_g": c[2], "E_la": c[3]}
 
+    def graph_path(self) -> str:
+        """which way the actor CSR of this graph was built: "direct" -- the edge list was in dataset order (per scene
+        permutations(range(n), 2), scenes ascending) and the CSR was written from the closed form -- or "general" (histogram,
+        scatter, row sort).  Decided on the device; reading it is a host synchronisation, like true_counts()."""
+        st = getattr(self, "count_stream", None)
+        if st is not None:
+            with torch.cuda.stream(st):
+                c = self._i32(self.ws, self.graph.counts, 8).tolist()
+        else:
+            c = self._i32(self.ws, self.graph.counts, 8).tolist()
+        return "direct" if c[6] == 1 else "general"
+
     def make_exact(self) -> "GraphContext":
         """turn a sync-free graph into an exact one in place: read the counts (synchronises) and store them in the E_* fields.
         The buffers keep their bound-sized allocation; every entry point accepts the graph afterwards."""
