@@ -1,4 +1,4 @@
-"""child process of test_gpu_range_guard.py: the kernel switches (TRAJSDE_NODE_FP32, the alternative library's forms) and TRAJSDE_LIB
+"""child process of test_gpu_range_guard.py: the kernel switches (TRAJSDE_NODE_FP32) and TRAJSDE_LIB
 are read once per process, so the cells of the site x route table that depend on them run here.  `cells SITE ...`: the `infer` (and
 `exact`) cell of each site under the forms the environment selects; `strict V ...`: every site's plant at the magnitudes V through the
 bf16x6 library TRAJSDE_LIB names.  Prints the "[range-guard]" lines of the cells and one JSON verdict line; an assertion that fails ends

@@ -2,7 +2,6 @@
 parts that need no GPU: the extension header against `_lib.CLIP_EXT_SIGNATURES`, the exported symbols, the size query and the
 refusals of the host side, the coefficient formula against torch.nn.utils.clip_grad_norm_, the torch routes of the training handles
 on CPU parameters, the command-line flag and the meaning of `gradient_clip_val`."""
-import ctypes
 import math
 import os
 import re
@@ -56,9 +55,9 @@ def test_clip_header_and_its_signature_table_agree(tmp_path):
 
 def test_the_three_symbols_are_exported_by_the_built_libraries():
     from trajsde_amd import _lib
-    lib, alt = _lib.lib(), ctypes.CDLL(_lib.ALT_LIB_PATH)
+    lib = _lib.lib()
     for name in NAMES:
-        assert hasattr(lib, name) and hasattr(alt, name), name
+        assert hasattr(lib, name), name
         assert getattr(lib, name).argtypes == _lib.CLIP_EXT_SIGNATURES[name][1]
 
 

@@ -26,8 +26,7 @@ def _model(modules, support=None, K=3, T=5, method=None):
 def test_extension_header_and_its_signature_table_agree(tmp_path):
     """include/trajsde_hip_cotangent_sel.h against `_lib.COT_SEL_EXT_SIGNATURES`, by the rules tests/test_cotangent_cpu.py applies to
     trajsde_hip_cotangent.h: the same names; argument counts, scalar types, pointer-ness and pointed-to structs, compared in Python and by
-    the C compiler; both libraries export the symbols; the table overlaps no other table, the header no other header"""
-    import ctypes
+    the C compiler; the library exports the symbols; the table overlaps no other table, the header no other header"""
     import os
     import re
 
@@ -57,9 +56,9 @@ def test_extension_header_and_its_signature_table_agree(tmp_path):
     # the dense entry point's arguments plus one pointer in front of the stream
     dense = _lib.EXT_SIGNATURES["trajsde_decoder_cotangent_backward"][1]
     assert _lib.COT_SEL_EXT_SIGNATURES["trajsde_decoder_cotangent_backward_sel"][1] == dense[:-1] + [_lib.P] + dense[-1:]
-    lib, alt = _lib.lib(), ctypes.CDLL(_lib.ALT_LIB_PATH)
+    lib = _lib.lib()
     for name in declared:
-        assert hasattr(lib, name) and hasattr(alt, name), name
+        assert hasattr(lib, name), name
     assert lib.trajsde_abi_version() == 10
 
 

@@ -690,12 +690,11 @@ def _run_child(args, env):
 
 
 def test_every_kernel_form_keeps_the_contract(dev):
-    """the switch matrix of test_gpu_trained_weights (the alternative library for its _ALT_MODES): one child interpreter per form, one
-    after the other, each with one mixed and one degenerate batch, forward and training step"""
+    """the switch matrix of test_gpu_trained_weights: one child interpreter per form, one after the other, each with one mixed and
+    one degenerate batch, forward and training step"""
     import test_gpu_trained_weights as W
-    from trajsde_amd import _lib
     for mode, env in W._MODES:
-        v = _run_child(["forms"], dict(env, TRAJSDE_LIB=_lib.ALT_LIB_PATH) if mode in W._ALT_MODES else env)
+        v = _run_child(["forms"], env)
         print(f"[memory-contract] kernel form {mode}: {v}")
 
 

@@ -708,27 +708,18 @@ def test_alternative_kernel_paths_agree(dev, tmp_path):
                                                "TRAJSDE_RECUR_LEGACY": "1", "TRAJSDE_GLOBAL_UNFUSED": "1"}),
                       ("one_tile", {"TRAJSDE_EDGE_PAIR": "0"}),
                       ("two_kernel", {"TRAJSDE_ATTN_FUSED": "0"}),
-                      ("fused_one_tile", {"TRAJSDE_FUSED_TILES": "1"}),
-                      ("gattn_mm", {"TRAJSDE_GATTN_MM": "1"}),
                       ("gattn_vector", {"TRAJSDE_GATTN_F32MM": "0", "TRAJSDE_REL_SPLIT": "0"}),
                       ("gattn_f32", {"TRAJSDE_REL_SPLIT": "0"}),
                       ("rel_split", {"TRAJSDE_REL_SPLIT": "1"}),
                       ("rel_split_scene_cache", {"TRAJSDE_REL_SPLIT": "2"}),
-                      ("gattn_two_tiles", {"TRAJSDE_GMF_TILES": "2", "TRAJSDE_REL_SPLIT": "0"}),
-                      ("pipelined", {"TRAJSDE_EDGE_PIPE": "1"}),
-                      ("tile32", {"TRAJSDE_EDGE_TILE": "32"}),
-                      ("tile32_pingpong", {"TRAJSDE_EDGE_TILE": "32", "TRAJSDE_EDGE_PINGPONG": "1"}),
                       ("fallbacks", {"TRAJSDE_RECUR_LEGACY": "1", "TRAJSDE_GLOBAL_UNFUSED": "1", "TRAJSDE_NODE_FP32": "0"})):
         path = str(tmp_path / (mode + ".pt"))
-        if mode in ("fused_one_tile", "gattn_mm", "gattn_two_tiles", "pipelined", "tile32", "tile32_pingpong"):
-            from trajsde_amd import _lib              # alternative kernel forms: not in the product library (trajsde_amd/build.py)
-            env = dict(env, TRAJSDE_LIB=_lib.ALT_LIB_PATH)
         subprocess.run([sys.executable, "-c", script, path], check=True, env={**os.environ, **env}, timeout=600)
         outs[mode] = torch.load(path)
-    # ... and the product library refuses a switch whose kernel it does not carry instead of silently running the default
+    # ... and the library refuses a switch whose kernel form it no longer carries instead of silently running the default
     r = subprocess.run([sys.executable, "-c", script, str(tmp_path / "refused.pt")], env={**os.environ, "TRAJSDE_EDGE_TILE": "32"},
                        capture_output=True, text=True, timeout=600)
-    assert r.returncode != 0 and "libtrajsde_alt.so" in r.stderr
+    assert r.returncode != 0 and "TRAJSDE_EDGE_TILE" in r.stderr
     for key in ("loc", "pi", "diff_in", "diff_out"):
         assert H.maxdiff(outs["split"][key], outs["fp32"][key]) <= 2e-5, key
         assert H.maxdiff(outs["split"][key], outs["fallbacks"][key]) <= 2e-5, key      # two-launch recurrence, unfused global attention, two-half FFN
@@ -736,9 +727,6 @@ def test_alternative_kernel_paths_agree(dev, tmp_path):
         # same products, a different order of the softmax accumulation
         assert H.maxdiff(outs["split"][key], outs["two_kernel"][key]) <= 2e-5, key
         assert torch.equal(outs["two_kernel"][key], outs["one_tile"][key]), key        # two tiles per wave: the same bits
-        assert torch.equal(outs["split"][key], outs["fused_one_tile"][key]), key         # 16 waves x 1 tile: the same streams, the same bits
-        # the global attention on the matrix cores (gattn.hip): logits and weighted sums as split products over 16-edge tiles
-        assert H.maxdiff(outs["split"][key], outs["gattn_mm"][key]) <= 2e-5, key
         # the fp32-matrix global attention (gattn_f32.hip) against the vector form it replaced (attn.hip k_global_attn)
         assert H.maxdiff(outs["gattn_f32"][key], outs["gattn_vector"][key]) <= 2e-5, key
         # the default global attention since the end of round 6 (gattn_h3.hip k_global_attn_sc: fp16x3 products on rel / node rows that
@@ -749,13 +737,6 @@ def test_alternative_kernel_paths_agree(dev, tmp_path):
         assert H.maxdiff(outs["split"][key], outs["rel_split"][key]) <= 2e-5, key
         # ... and the explicit switch is the default
         assert torch.equal(outs["split"][key], outs["rel_split_scene_cache"][key]), key
-        # ... and against its 32-edges-a-step form (k_global_attn_mf2: two tiles of a target through every phase together)
-        assert H.maxdiff(outs["split"][key], outs["gattn_two_tiles"][key]) <= 2e-5, key
-        assert torch.equal(outs["split"][key], outs["pipelined"][key]), key              # k_edge_attn2p: the tiles one stage apart, the same bits
-        # the fused edge attention on 32x32x16 matrix tiles (edge32.hip): other fragment order, same algebra; with and without the
-        # phase barriers between the two waves of a SIMD: the same bits
-        assert H.maxdiff(outs["split"][key], outs["tile32"][key]) <= 2e-5, key
-        assert torch.equal(outs["tile32"][key], outs["tile32_pingpong"][key]), key
 
 
 @pytest.mark.parametrize("scale", [1e-6, 1e-3, 1.0, 30.0, 1e3, 1e4])

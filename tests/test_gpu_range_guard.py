@@ -494,19 +494,12 @@ class Case:
         self.inf = inf                      # False: +inf does not reach the site as +inf on this route (the cell's `note` says why)
 
 
-ROUTES = ("infer", "exact", "node_fp32=0", "node_fp32=1", "alt", "train_fwd", "bwd_recompute", "ood", "milstein", "bf16",
+ROUTES = ("infer", "exact", "node_fp32=0", "node_fp32=1", "train_fwd", "bwd_recompute", "ood", "milstein", "bf16",
           "vanilla_fwd", "vanilla_bwd")
 # the child-process routes: environment of the child (tests/range_guard_child.py runs the `infer` cell of every site under it)
-ALT = "<alt>"
 CHILD_FORMS = {
     "node_fp32=0": [("node_fp32=0", {"TRAJSDE_NODE_FP32": "0"})],
     "node_fp32=1": [("node_fp32=1", {"TRAJSDE_NODE_FP32": "1"})],
-    # the alternative library's forms (test_gpu_trained_weights._ALT_MODES): other edge-attention and global-attention kernels in front
-    # of the same node block
-    "alt": [(m, dict(e, TRAJSDE_LIB=ALT)) for m, e in (("fused_one_tile", {"TRAJSDE_FUSED_TILES": "1"}), ("gattn_mm", {"TRAJSDE_GATTN_MM": "1"}),
-                                                       ("gattn_two_tiles", {"TRAJSDE_GMF_TILES": "2", "TRAJSDE_REL_SPLIT": "0"}),
-                                                       ("pipelined", {"TRAJSDE_EDGE_PIPE": "1"}), ("tile32", {"TRAJSDE_EDGE_TILE": "32"}),
-                                                       ("tile32_pingpong", {"TRAJSDE_EDGE_TILE": "32", "TRAJSDE_EDGE_PINGPONG": "1"}))],
 }
 IN_CHILD = "in the child process"          # cell marker: the case is the `infer` case of the row, run under CHILD_FORMS[route]
 
@@ -527,9 +520,8 @@ TABLE = {
     "DEC_STATE": {
         "infer": Case("dec_state", run_infer, entry=("trajsde_decoder_forward",)),
         "exact": "the exact graph stage changes list lengths, not the decoder (runtime.set_sync_free): the `infer` case",
-        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
-        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
-        "alt": "libtrajsde_alt.so differs in attn.hip, edge32.hip, gattn*.hip, stages.hip (build.ALT_SOURCES): decoder.hip is the same object",
+        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:117-123); the decoder does not read it",
+        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:117-123); the decoder does not read it",
         "train_fwd": "training runs the inference decoder forward (model._forward_stages): the `infer` case; run_training_step runs it too",
         "bwd_recompute": Case("dec_state", run_dec_stage("l2"), compare=False,
                               entry=("trajsde_decoder_l2_backward",), note="k_sde_replay_coop / k_sde_replay note the replayed states"),
@@ -542,9 +534,8 @@ TABLE = {
     "DEC_INPUT": {
         "infer": Case("dec_input", run_infer),
         "exact": Case("dec_input", run_exact),
-        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
-        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the decoder does not read it",
-        "alt": "libtrajsde_alt.so differs in attn.hip, edge32.hip, gattn*.hip, stages.hip (build.ALT_SOURCES): decoder.hip is the same object",
+        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:117-123); the decoder does not read it",
+        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:117-123); the decoder does not read it",
         "train_fwd": Case(None, run_dec_stage("forward"), entry=("trajsde_decoder_forward",)),
         "bwd_recompute": Case(None, run_dec_stage("cot"), compare=False, entry=("trajsde_decoder_cotangent_backward",),
                               note="k_init_all; l2 / nll / sel (k_init_sel) in test_decoder_backward_entry_points_refuse_a_large_embedding"),
@@ -558,9 +549,8 @@ TABLE = {
     "ENC_STATE": {
         "infer": Case("enc_state", run_infer, entry=("trajsde_encoder_forward",)),
         "exact": Case("enc_state", run_exact),
-        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the recurrence does not read it",
-        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:114-120); the recurrence does not read it",
-        "alt": IN_CHILD,
+        "node_fp32=0": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:117-123); the recurrence does not read it",
+        "node_fp32=1": "TRAJSDE_NODE_FP32 selects k_node_update / k_ffn forms (stages.hip:117-123); the recurrence does not read it",
         "train_fwd": Case("enc_state", run_enc_train, entry=("trajsde_encoder_forward_train",), note="k_enc_recur_coop<.., save>"),
         "bwd_recompute": Case("enc_state", run_enc_bwd, compare=False, entry=("trajsde_encoder_backward",)),
         "ood": Case("enc_state", run_ood, entry=("trajsde_encoder_forward_ood",)),
@@ -574,21 +564,19 @@ TABLE = {
         "exact": _same_forward("ENC_STATE, DEC_INPUT, NODE_AGG and FFN_HIDDEN"),
         "node_fp32=0": IN_CHILD,
         "node_fp32=1": IN_CHILD,
-        "alt": IN_CHILD,
         "train_fwd": Case("enc_input", run_enc_train),
         "bwd_recompute": Case("enc_input", run_enc_cot_bwd, compare=False, entry=("trajsde_encoder_cotangent_backward",)),
         "ood": Case("enc_input", run_ood),
         "milstein": _DEC_ONLY,
         "bf16": Case("enc_input", run_bf16, compare=False, note=_BF16_ROWS),
-        "vanilla_fwd": "no recurrence: aa_out goes through k_tr_prep (an add, grid.hip:27) into k_node_proj's LayerNorm (stages.hip:440)",
-        "vanilla_bwd": "no recurrence: aa_out goes through k_tr_prep (an add, grid.hip:27) into k_node_proj's LayerNorm (encoder_bwd.hip:1212)",
+        "vanilla_fwd": "no recurrence: aa_out goes through k_tr_prep (an add, grid.hip:27) into k_node_proj's LayerNorm (stages.hip:421)",
+        "vanilla_bwd": "no recurrence: aa_out goes through k_tr_prep (an add, grid.hip:27) into k_node_proj's LayerNorm (encoder_bwd.hip:1215)",
     },
     "NODE_AGG": {
         "infer": Case("enc_node_agg", run_infer),
         "exact": Case("agg_node_agg", run_exact, entry=("trajsde_aggregator_forward_heads",), inf=False, note=_INF_NAN),
         "node_fp32=0": IN_CHILD,
         "node_fp32=1": IN_CHILD,
-        "alt": IN_CHILD,
         "train_fwd": Case("agg_node_agg", run_agg_train, entry=("trajsde_aggregator_forward_train",), inf=False, note="k_node_update<true>; " + _INF_NAN),
         "bwd_recompute": Case("agg_node_agg", run_agg_bwd, compare=False, entry=("trajsde_aggregator_backward_heads",), inf=False, note=_INF_NAN),
         "ood": Case("enc_node_agg", run_ood),
@@ -602,22 +590,20 @@ TABLE = {
         "exact": Case("agg_ffn", run_exact),
         "node_fp32=0": IN_CHILD,
         "node_fp32=1": IN_CHILD,
-        "alt": IN_CHILD,
         "train_fwd": Case("agg_ffn", run_agg_train, note="k_ffn6 (aggregator_bwd.hip:1061); the encoder's in test_training_forwards_note_the_ffn"),
         "bwd_recompute": Case("enc_ffn", run_enc_bwd, compare=False, note="k_ffn6 (encoder_bwd.hip:850)"),
         "ood": Case("enc_ffn", run_ood),
         "milstein": _DEC_ONLY,
         "bf16": _BF16_ROWS + "; the hidden units never leave registers",
-        "vanilla_fwd": Case("grid_tr_ffn", run_grid_plain_encoder, model="grid", entry=("trajsde_encoder_grid_forward",), note="k_ffn (stages.hip:445)"),
+        "vanilla_fwd": Case("grid_tr_ffn", run_grid_plain_encoder, model="grid", entry=("trajsde_encoder_grid_forward",), note="k_ffn (stages.hip:426)"),
         "vanilla_bwd": Case("grid_tr_ffn", run_grid_enc_bwd(False), model="grid", compare=False, entry=("trajsde_encoder_grid_backward",),
-                            note="k_ffn (encoder_bwd.hip:1218)"),
+                            note="k_ffn (encoder_bwd.hip:1221)"),
     },
     "WEIGHT": {
         "infer": Case("agg_weight", run_infer, entry=("trajsde_pack_weights",)),
         "exact": _PACK,
         "node_fp32=0": IN_CHILD,
         "node_fp32=1": IN_CHILD,
-        "alt": IN_CHILD,
         "train_fwd": Case("agg_weight", run_training_step, compare=False, entry=("trajsde_pack_weights_many",),
                           note="the step's six images in one packing call (runtime.PackSet)"),
         "bwd_recompute": _PACK,
@@ -731,8 +717,6 @@ _CHILD_RESULTS = {}
 
 
 def run_child(args, env):
-    from trajsde_amd import _lib
-    env = {k: (_lib.ALT_LIB_PATH if v == ALT else v) for k, v in env.items()}
     drop = ("TRAJSDE_LIB", "TRAJSDE_NODE_FP32")
     r = subprocess.run([sys.executable, _CHILD] + list(args), env={**{k: v for k, v in os.environ.items() if k not in drop}, **env},
                        timeout=600, capture_output=True, text=True)

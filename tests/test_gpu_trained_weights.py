@@ -203,18 +203,11 @@ _MODES = (("split", {}),
                     "TRAJSDE_GLOBAL_UNFUSED": "1"}),
           ("one_tile", {"TRAJSDE_EDGE_PAIR": "0"}),
           ("two_kernel", {"TRAJSDE_ATTN_FUSED": "0"}),
-          ("fused_one_tile", {"TRAJSDE_FUSED_TILES": "1"}),
-          ("gattn_mm", {"TRAJSDE_GATTN_MM": "1"}),
           ("gattn_vector", {"TRAJSDE_GATTN_F32MM": "0", "TRAJSDE_REL_SPLIT": "0"}),
           ("gattn_f32", {"TRAJSDE_REL_SPLIT": "0"}),
           ("rel_split", {"TRAJSDE_REL_SPLIT": "1"}),
           ("rel_split_scene_cache", {"TRAJSDE_REL_SPLIT": "2"}),
-          ("gattn_two_tiles", {"TRAJSDE_GMF_TILES": "2", "TRAJSDE_REL_SPLIT": "0"}),
-          ("pipelined", {"TRAJSDE_EDGE_PIPE": "1"}),
-          ("tile32", {"TRAJSDE_EDGE_TILE": "32"}),
-          ("tile32_pingpong", {"TRAJSDE_EDGE_TILE": "32", "TRAJSDE_EDGE_PINGPONG": "1"}),
           ("fallbacks", {"TRAJSDE_RECUR_LEGACY": "1", "TRAJSDE_GLOBAL_UNFUSED": "1", "TRAJSDE_NODE_FP32": "0"}))
-_ALT_MODES = ("fused_one_tile", "gattn_mm", "gattn_two_tiles", "pipelined", "tile32", "tile32_pingpong")
 
 _CHILD = (
     "import sys, torch; sys.path[:0] = [%r, %r, %r]\n"
@@ -253,10 +246,8 @@ def _forms_against_oracle(tmp_path, modes, name="mixed_k6_t20"):
 
 def test_every_kernel_form_matches_float64_oracle(dev, tmp_path):
     """the switch matrix of test_gpu_parity.test_alternative_kernel_paths_agree at both strengths, one interpreter per mode (the
-    switches are read once per process), the alternative library included -- each form against the float64 oracle, not only
-    against the others"""
-    from trajsde_amd import _lib
-    _forms_against_oracle(tmp_path, [(m, dict(e, TRAJSDE_LIB=_lib.ALT_LIB_PATH) if m in _ALT_MODES else e) for m, e in _MODES])
+    switches are read once per process) -- each form against the float64 oracle, not only against the others"""
+    _forms_against_oracle(tmp_path, _MODES)
 
 
 def test_strict24_library_matches_float64_oracle(dev, tmp_path):
@@ -270,9 +261,7 @@ def test_strict24_library_matches_float64_oracle(dev, tmp_path):
 def test_every_kernel_form_under_irregular_masks(dev, tmp_path):
     """the legacy and the cooperative recurrence, the gathering and the scene-cached global attention each carry mask code of their
     own: the same switch matrix on the irregular batch (masked GRU steps before the kept iteration, agents without global edges)"""
-    from trajsde_amd import _lib
-    _forms_against_oracle(tmp_path, [(m, dict(e, TRAJSDE_LIB=_lib.ALT_LIB_PATH) if m in _ALT_MODES else e) for m, e in _MODES],
-                          name="irregular_k6_t20")
+    _forms_against_oracle(tmp_path, _MODES, name="irregular_k6_t20")
 
 
 def test_strict24_library_under_irregular_masks(dev, tmp_path):

@@ -92,8 +92,7 @@ def test_entry_point_refuses_bad_arguments_before_any_launch():
 
 def test_grid_extension_header_and_its_signature_table_agree(tmp_path):
     """include/trajsde_hip_grid_cotangent.h against `_lib.GRID_EXT_SIGNATURES`, by the rules tests/test_cabi_cpu.py applies to
-    trajsde_hip.h and `_lib.SIGNATURES` (its helpers, imported); both libraries export the symbols; no table or header overlaps another"""
-    import ctypes
+    trajsde_hip.h and `_lib.SIGNATURES` (its helpers, imported); the library exports the symbols; no table or header overlaps another"""
     import os
     import re
 
@@ -120,9 +119,9 @@ def test_grid_extension_header_and_its_signature_table_agree(tmp_path):
     bad["trajsde_mlp_decoder_cotangent_backward"] = (res, args[:-1])
     assert CABI._check_against_header(bad, protos)
     assert CABI._compile_tu(swap(CABI._prototype_tu(bad, protos)), tmp_path, H.ROOT, "gridcot_bad").returncode != 0
-    lib, alt = _lib.lib(), ctypes.CDLL(_lib.ALT_LIB_PATH)
+    lib = _lib.lib()
     for name in declared:
-        assert hasattr(lib, name) and hasattr(alt, name), name
+        assert hasattr(lib, name), name
 
 
 def test_routes_and_reached_parameters():

@@ -136,7 +136,7 @@ def test_milstein_decode_kernels_compile_without_scratch(tmp_path, extra, expect
     flags = [f for f in build.FLAGS if f != "-fPIC"]
     out = tmp_path / "decoder.s"
     src = os.path.join(H.ROOT, "trajsde_amd", "csrc", "decoder.hip")
-    subprocess.check_call([build.HIPCC, *flags, "-DTSDE_PRODUCT=1", *extra, "--cuda-device-only", "-S", "-o", str(out), src],
+    subprocess.check_call([build.HIPCC, *flags, *extra, "--cuda-device-only", "-S", "-o", str(out), src],
                           stderr=subprocess.DEVNULL)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN4tsde12k_sde_decodeILb[01]ELi\d+ELb1E\w+):.*?; ScratchSize: (\d+)", text, flags=re.S | re.M)

@@ -154,7 +154,7 @@ def test_milstein_backward_kernels_compile_without_scratch(tmp_path, extra):
     flags = [f for f in build.FLAGS if f != "-fPIC"]
     out = tmp_path / "decoder_mil_bwd.s"
     src = os.path.join(H.ROOT, "trajsde_amd", "csrc", "decoder_mil_bwd.hip")
-    subprocess.check_call([build.HIPCC, *flags, "-DTSDE_PRODUCT=1", *extra, "--cuda-device-only", "-S", "-o", str(out), src],
+    subprocess.check_call([build.HIPCC, *flags, *extra, "--cuda-device-only", "-S", "-o", str(out), src],
                           stderr=subprocess.DEVNULL)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN4tsde\d+k_(?:sde_replay_mil|sde_bwd_mil|add_mil_wgrad)\w+):.*?; ScratchSize: (\d+)", text,

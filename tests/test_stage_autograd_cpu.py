@@ -24,10 +24,9 @@ def _cfg(K=3, T=5, max_t=0.5, **decoder_kw):
 
 
 def test_the_symbol_is_exported_by_the_built_libraries():
-    import ctypes
     from trajsde_amd import _lib
-    lib, alt = _lib.lib(), ctypes.CDLL(_lib.ALT_LIB_PATH)
-    assert hasattr(lib, NAME) and hasattr(alt, NAME)
+    lib = _lib.lib()
+    assert hasattr(lib, NAME)
     assert getattr(lib, NAME).argtypes == _lib.ENC_COT_EXT_SIGNATURES[NAME][1]
     assert lib.trajsde_abi_version() == 10
 

@@ -1,7 +1,7 @@
 """Price the loop of a kernel from its gfx950 listing with the per-instruction SIMD costs that tools/microbench/vissue.hip measured
 (profiles/r06_microbench_vissue.log): the static counterpart of a phase-stamp run.
 
-    hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -DTSDE_NO_SLP=1 -DTSDE_PRODUCT=1 -std=c++17 --cuda-device-only -S -o /tmp/attn.s trajsde_amd/csrc/attn.hip
+    hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -DTSDE_NO_SLP=1 -std=c++17 --cuda-device-only -S -o /tmp/attn.s trajsde_amd/csrc/attn.hip
     python tools/issue_model.py /tmp/attn.s k_edge_attn2ILi2ELb0ELb0ELi0ELb1E [--loop N] [--mfma-hold 5.2]
 
 For every backward-branch loop of the kernel (or the N-th largest) it prints the instruction count by cost class and three sums:

@@ -20,9 +20,6 @@ TABLES = {
                                       "P3 drift out, EM update", "  barrier", "P4 GRU gates first layers", "  barrier",
                                       "P5 gates, r*h", "  barrier", "P6 candidate first layer", "  barrier",
                                       "P7 candidate out, blend", "  barrier", "top: x_t loads, noise, biases", "-"]),
-    "gattn": (8, "16-edge tiles", ["issue the loads of the tiles ahead", "wait for this tile's rel / k_node rows", "splits + stage writes",
-                                   "P1: fragment reads + 12 matrix instr.", "softmax", "P2: splits + 16 matrix instr.", "loop overhead",
-                                   "per-target epilogue (W_ve, store)"]),
     "gh3": (8, "16-edge tiles", ["loop overhead", "wait for this tile's rows (sc: rel rows + indices)", "h3: P1 | sc: parking + requests of the tiles ahead",
                                  "h3: v rows, softmax, split | sc: P1", "h3: P2 | sc: softmax", "h3: loop exit | sc: P2",
                                  "per-target prologue + epilogue (sc: and the unit's staging)", "-"]),

@@ -2,7 +2,7 @@
 the compiler's listing, times the measured issue cost of each class (tools/microbench/, profiles/r03_microbench_*.log) = SIMD cycles,
 against the in-kernel phase clocks (profiles/r04_sde_step_phase_stamps.log).  Writes the table of profiles/r05_sde_step_floor.md.
 
-    hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -DTSDE_NO_SLP=1 -DTSDE_PRODUCT=1 -std=c++17 --cuda-device-only -S -o /tmp/dec.s trajsde_amd/csrc/decoder.hip
+    hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -DTSDE_NO_SLP=1 -std=c++17 --cuda-device-only -S -o /tmp/dec.s trajsde_amd/csrc/decoder.hip
     python tools/sde_step_floor.py /tmp/dec.s [stamped SIMD cycles per tile-step = 5912] [measured HBM fraction = 0.304]
 """
 import collections

@@ -1,4 +1,5 @@
-"""Build libtrajsde_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libtrajsde_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU): one library with one form of every
+kernel, plus its strict-precision twin (`--strict`, below).
 
     python -m trajsde_amd.build [--force]
     TRAJSDE_SPLIT=bf16x6 python -m trajsde_amd.build --force     # three bf16 pieces / six products instead of fp16x3
@@ -10,13 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtrajsde_hip.so")
-# The product library carries ONE form of every kernel (-DTSDE_PRODUCT).  The measured-slower alternative forms that are kept as
-# cross-checks -- the 32x32x16 edge attention (edge32.hip), the software-pipelined and the one-tile edge attention, the matrix-core
-# global attention (gattn.hip) -- are compiled into a second library of the same C-ABI, loaded (TRAJSDE_LIB) by the tests and A/B
-# tools that select them with their TRAJSDE_* switches; the product library refuses those switches.
-ALT_LIB = os.path.join(HERE, "variants", "libtrajsde_alt.so")
-ALT_SOURCES = ("attn.hip", "edge32.hip", "gattn.hip", "gattn_f32.hip", "stages.hip")     # the units TSDE_PRODUCT changes
-# The strict-precision twin: the product library with 24-bit operands (three bf16 pieces, six products: -DTSDE_SPLIT_H3=0), same
+# The strict-precision twin: the library with 24-bit operands (three bf16 pieces, six products: -DTSDE_SPLIT_H3=0), same
 # C-ABI.  bench.py times it in a child process (`strict24` key of the bench line) so that the headline's precision asterisk --
 # fp16x3 operands are 22-bit -- always has a current number beside it.  Not built when TRAJSDE_SPLIT already selects bf16x6.
 STRICT_LIB = os.path.join(HERE, "variants", "libtrajsde_strict24.so")
@@ -78,7 +73,7 @@ def _deps():
 
 
 def _stale() -> bool:
-    if not os.path.isfile(LIB) or not os.path.isfile(ALT_LIB):
+    if not os.path.isfile(LIB):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(d) > t for d in _deps())
@@ -109,7 +104,7 @@ def _unit_flags(name):
 
 
 def build_strict(force: bool = False, verbose: bool = True) -> str:
-    """variants/libtrajsde_strict24.so: the product library with 24-bit operands (three bf16 pieces, six products), same C-ABI"""
+    """variants/libtrajsde_strict24.so: the library with 24-bit operands (three bf16 pieces, six products), same C-ABI"""
     if "-DTSDE_SPLIT_H3=0" in FLAGS:
         raise RuntimeError("TRAJSDE_SPLIT=bf16x6 already builds the main library strict")
     if not force and os.path.isfile(STRICT_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(STRICT_LIB) for d in _deps()):
@@ -120,7 +115,7 @@ def build_strict(force: bool = False, verbose: bool = True) -> str:
         objs.append(sobj)
         # (without the per-file options: the bf16x6 recurrence pins nothing in the accumulation registers, and this compiler
         #  crashes on its fp32 matrix instructions under -amdgpu-mfma-vgpr-form)
-        jobs.append((src, [HIPCC, *FLAGS, "-DTSDE_SPLIT_H3=0", "-DTSDE_PRODUCT=1", "-c", src, "-o", sobj]))
+        jobs.append((src, [HIPCC, *FLAGS, "-DTSDE_SPLIT_H3=0", "-c", src, "-o", sobj]))
     for out in _run_all(jobs):
         if verbose and out.strip():
             print(out.decode())
@@ -134,34 +129,25 @@ def build_strict(force: bool = False, verbose: bool = True) -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     if not force and not _stale():
         return LIB
-    objs, alt_objs, jobs = [], [], []
+    objs, jobs = [], []
     for src in sources():
         name = os.path.basename(src)
-        extra = _unit_flags(name)
         obj = os.path.join(CSRC, name[:-4] + ".o")
         objs.append(obj)
-        jobs.append((src, [HIPCC, *FLAGS, "-DTSDE_PRODUCT=1", *extra, "-c", src, "-o", obj]))
-        if name in ALT_SOURCES:                              # the same unit with the alternative forms compiled in
-            alt = os.path.join(CSRC, name[:-4] + ".alt.o")
-            alt_objs.append(alt)
-            jobs.append((src, [HIPCC, *FLAGS, *extra, "-c", src, "-o", alt]))
-        else:
-            alt_objs.append(obj)
+        jobs.append((src, [HIPCC, *FLAGS, *_unit_flags(name), "-c", src, "-o", obj]))
     for out in _run_all(jobs):
         if verbose and out.strip():
             print(out.decode())
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
-    os.makedirs(os.path.dirname(ALT_LIB), exist_ok=True)
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", ALT_LIB, *alt_objs])
     if verbose:
-        print(f"built {LIB}\nbuilt {ALT_LIB}")
+        print(f"built {LIB}")
     if _want_strict():
         build_strict(force=True, verbose=verbose)
     return LIB
 
 
 def build_sanitized(out_lib: str, obj_dir: str) -> str:
-    """The product library once more with the HOST side under AddressSanitizer + UndefinedBehaviorSanitizer (device code
+    """The library once more with the HOST side under AddressSanitizer + UndefinedBehaviorSanitizer (device code
     unsanitised: -fno-gpu-sanitize; GPU ASan is not available on this pool).  For the CPU suite (tests/test_cabi_cpu.py): the
     size queries, argument checks, job tables and workspace carving of the entry points run on the host and can be driven
     without a GPU.  Load it in a process started with LD_PRELOAD=<asan_runtime()>."""
@@ -171,7 +157,7 @@ def build_sanitized(out_lib: str, obj_dir: str) -> str:
     for src in sources():
         obj = os.path.join(obj_dir, os.path.basename(src)[:-4] + ".san.o")
         objs.append(obj)
-        jobs.append((src, [HIPCC, *FLAGS, "-DTSDE_PRODUCT=1", *san, "-c", src, "-o", obj]))
+        jobs.append((src, [HIPCC, *FLAGS, *san, "-c", src, "-o", obj]))
     _run_all(jobs, "hipcc (sanitized)")
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", *san, "-o", out_lib, *objs])
     return out_lib

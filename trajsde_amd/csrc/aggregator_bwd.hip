@@ -1084,6 +1084,7 @@ int trajsde_aggregator_backward(const trajsde_batch* b, const trajsde_graph* g, 
 int trajsde_aggregator_forward_train(const trajsde_batch* b, const trajsde_graph* g, const float* blob_fwd, int num_layers, int num_modes,
                                      int num_heads, const float* local_embed, void* ws, int64_t ws_bytes, float* global_embed,
                                      const trajsde_dropout* dropout, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && blob_fwd && local_embed && ws && global_embed, "aggregator_forward_train: null pointer");
   TS_REQUIRE(num_heads == 8 || num_heads == 4, "aggregator_forward_train: num_heads must be 8 or 4");
   TS_REQUIRE(g->g_src && g->g_segptr, "aggregator_forward_train: graph not compacted (call trajsde_graph_compact)");
@@ -1108,6 +1109,7 @@ int trajsde_aggregator_backward_heads(const trajsde_batch* b, const trajsde_grap
                                       int num_layers, int num_modes, int num_heads, const float* local_embed, const float* d_global,
                                       void* ws, int64_t ws_bytes, float* const* grads, int n_grads, float* d_local,
                                       const trajsde_dropout* dropout, int tape_valid, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && blob_fwd && blob_bwd && local_embed && d_global && ws && grads && d_local, "aggregator_backward: null pointer");
   TS_REQUIRE(!state_bf16(), "aggregator_backward: the backward pass keeps its tape in fp32; switch trajsde_state_storage(0) for training");
   TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), "aggregator_backward: dropout p must be in [0, 1)");

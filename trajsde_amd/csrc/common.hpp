@@ -15,6 +15,9 @@ namespace tsde {
 
 std::string& last_error_ref();
 int fail(int code, const std::string& msg);
+// TRAJSDE_ERR_UNSUPPORTED when the environment sets a switch of a kernel form that has been removed (stages.hip); first thing in
+// every encoder / aggregator entry point that launches
+int refuse_retired_switches();
 
 #define TS_HIP(expr)                                                                                  \
   do {                                                                                                \

@@ -933,6 +933,7 @@ int64_t trajsde_encoder_backward_scratch_bytes(const trajsde_batch* b, const tra
 int trajsde_encoder_forward_train(const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob_fwd,
                                   const float* step_tab /*HOST [H,8]*/, const trajsde_noise* noise, void* ws, int64_t ws_bytes,
                                   float* local_embed, float* diff_pick, const trajsde_dropout* dropout, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob_fwd && step_tab && ws && local_embed && diff_pick, "encoder_forward_train: null pointer");
   TS_REQUIRE(g->aa_dst && g->la_dst && g->orig, "encoder_forward_train: graph not compacted (call trajsde_graph_compact)");
   TS_REQUIRE(g->exact, "encoder_forward_train: needs exact list lengths (trajsde_graph_prepare, not _async)");
@@ -1112,6 +1113,7 @@ int trajsde_encoder_backward(const trajsde_batch* b, const trajsde_graph* g, con
                              const trajsde_noise* noise, const float* d_local, float diff_weight, void* ws, int64_t ws_bytes,
                              float* diff_loss, float* const* grads, int n_grads, float* d_latent, float* d_aa_out,
                              const trajsde_dropout* dropout, int tape_valid, void* scratch, int64_t scratch_bytes, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob_fwd && blob_bwd && step_tab && step_tab_dev && d_local && ws && diff_loss && grads,
              "encoder_backward: null pointer");
   // DiffBCE on the picked diffusion values
@@ -1170,6 +1172,7 @@ int trajsde_encoder_grid_backward(const trajsde_batch* b, const trajsde_graph* g
 int trajsde_encoder_grid_backward_train(const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob_fwd,
                                         const float* blob_bwd, int num_heads, int num_temporal_layers, const float* d_local, void* ws,
                                         int64_t ws_bytes, float* const* grads, int n_grads, const trajsde_dropout* dropout, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob_fwd && blob_bwd && d_local && ws && grads, "encoder_grid_backward: null pointer");
   TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), "encoder_grid_backward: dropout p must be in [0, 1)");
   const bool dropping = dropout && dropout->p > 0.f;

@@ -60,6 +60,7 @@ int trajsde_encoder_cotangent_backward(const trajsde_batch* b, const trajsde_gra
                                        const trajsde_noise* noise, const float* d_local, const float* d_diff_in, const float* d_diff_out,
                                        void* ws, int64_t ws_bytes, float* const* grads, int n_grads, float* d_latent, float* d_aa_out,
                                        const trajsde_dropout* dropout, int tape_valid, void* scratch, int64_t scratch_bytes, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob_fwd && blob_bwd && step_tab && step_tab_dev && d_local && ws && grads,
              "encoder_cotangent_backward: null pointer");
   const DldgProducer cot = [&](const float*, float* DLDG, float*, hipStream_t st) -> int {

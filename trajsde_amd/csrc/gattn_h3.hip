@@ -3,7 +3,7 @@
 //
 // Why.  The global interactor is 28 % of the one-stream forward and its attention (three layers) most of that.  The default kernel
 // (gattn_f32.hip) multiplies on the fp32 matrix instruction -- 32 x v_mfma_f32_16x16x4_f32 = 1 024 cycles of the matrix pipe per 16
-// edges -- because the fp16x3 form (gattn.hip, round 4) had to split every rel row twice inside the kernel (once per product, in two
+// edges -- because the earlier fp16x3 form (round 4, HISTORY.md section 5) had to split every rel row twice inside the kernel (once per product, in two
 // different pairings): 128 values a lane and tile, at what tools/microbench/vissue.hip now shows to be 10 SIMD cycles a value.  The
 // rel rows are written once per forward (attn.hip k_edge_embed2) and read by three layers: the split belongs to the writer.
 //
@@ -11,7 +11,7 @@
 // fp16(x - hi) (tile.hpp split_pair): `TRAJSDE_REL_SPLIT`, inference with fp32 state only (training keeps fp32 rows: its backward
 // kernels read them; bf16 state storage keeps bf16 rows).
 //
-// Kernel.  One wave per target, 16 in-edges a tile, the algebra and the hand-offs of gattn.hip:
+// Kernel.  One wave per target, 16 in-edges a tile, the algebra and the hand-offs of that earlier form:
 //   P1   logits [16 edges x 8 heads]  = [rel_e | k_node[src_e]] (K = 128) . W1         W1 = [U ; Q]: U_h = Wke_h^T q_h, Q = q masked to its head
 //   P2   O [8 heads x 128]           += alpha^T [heads x 16 edges] . [rel_e | v_node[src_e]]
 // The tile's 16 rel rows are loaded whole (16 B a lane, 16 lanes a row, two tiles ahead) and parked in a wave-private 4 KB LDS tile
@@ -20,10 +20,10 @@
 //     consecutive features 32 s + 8 g .. of piece p;
 //   * P2's B operand contracts over EDGES, the index the rows are not contiguous in: ds_read_b64_tr_b16 hands lane i of a 16-lane group
 //     column i (feature 16 cb + i) of the group's four rows (edges 4 g .. 4 g + 3) -- the high pieces in k-slots 0 .. 3, the low pieces
-//     in 4 .. 7 of one K = 32 instruction, against the weights' piece repeated in both halves (gattn.hip: all four terms of the split
+//     in 4 .. 7 of one K = 32 instruction, against the weights' piece repeated in both halves (all four terms of the split
 //     product in two instructions).
 // No vector instruction touches a rel value.  The gathered node rows (k_node, v_node: 2 MB a layer, L2-resident) stay fp32 and are split
-// here as in gattn.hip.
+// here.
 #include "attn_common.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -39,7 +39,7 @@ static unsigned long long* const g_stamps_gh3 = nullptr;
 #endif
 
 #if TSDE_SPLIT_H3
-constexpr float H3_LAZY = 8.0f;              // the running maximum follows a tile's maximum only past this margin (gattn.hip)
+constexpr float H3_LAZY = 8.0f;              // the running maximum follows a tile's maximum only past this margin
 
 // (timing experiments only: -DTSDE_H3_EXP=1 every gathered node row is row (index & 3), =2 every rel row is one of the segment's first 4)
 // (=4: a tile's softmax and second product use the previous tile's logits: the dataflow of a software pipeline; =8: no scheduling fences;
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(256, TSDE_H3_OCC) void k_global_attn_h3(const float
 #endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // ---- P1: the tile's logits, lane (head nn & 7, g): edges 4g .. 4g+3.  Three chains, one per term of the split product (gattn.hip)
+    // ---- P1: the tile's logits, lane (head nn & 7, g): edges 4g .. 4g+3.  Three chains, one per term of the split product
     f4 lg;
     {
       f4 t0 = f4{0.f, 0.f, 0.f, 0.f}, t1 = t0, t2 = t0;
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256, TSDE_H3_OCC) void k_global_attn_h3(const float
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     clk.mark(3);                                              // [3] v rows parked, softmax, the weights' split
-    // ---- P2 over the tile's 16 edges with K = 32 instructions (gattn.hip): B carries the rows' high pieces in slots 0..3 and their low
+    // ---- P2 over the tile's 16 edges with K = 32 instructions: B carries the rows' high pieces in slots 0..3 and their low
     //      pieces in 4..7 -- the transposing read hands lane i column 16 cb + i of the lane group's four rows --, A one piece of the weights
 #if TSDE_H3_SKIP & 4                                           // (timing only: no second product, no transposing reads)
 #pragma unroll

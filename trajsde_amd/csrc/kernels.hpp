@@ -93,8 +93,6 @@ inline AttnPlan attn_plan(int64_t E, int streams_target = SEG_STREAMS_512) {
 template <int NT, bool DROP, bool SAVE, int LIST, bool H8>
 __global__ void k_edge_attn2(const float* img, const float* geom, const int32_t* dst, const float* q, EdgeCount ec, int C, float* rec, int heads,
                              const int32_t* segptr, DropArg drop, float* emb_out);
-template <int LIST>
-__global__ void k_edge_attn2p(const float* img, const float* geom, const int32_t* dst, const float* q, EdgeCount ec, int C, float* rec, int heads);
 // host side of the fused edge attention (stages.hip): k_edge_attn2 + k_seg_merge -> agg [R,64]; the training path also asks
 // for the embedding rows (emb_out [E,64]) and the softmax statistics (stats [R,heads,2]).  img: the stage blob's EdgeL6F image
 bool attn_fused_enabled();
@@ -102,8 +100,6 @@ int64_t fused_rec_floats(int64_t E, bool exact, int64_t targets);
 int fused_edge_attention(const char* tag, bool dominant, const float* img, const float* geom, const int32_t* dst, const float* q,
                          const EdgeCount& ec, const int32_t* segptr, int64_t R, float* rec, float* agg, int heads, hipStream_t st,
                          const DropArg& drop, float* emb_out = nullptr, float* stats = nullptr, SegMerge* defer = nullptr);
-// the same attention on the matrix cores (gattn.hip): inference, 8 heads, fp32 rows, no dropout; an alternative, TRAJSDE_GATTN_MM=1 selects it
-bool gattn_mm_enabled();
 // gattn_h3.hip: the same attention as fp16x3 products on rel rows stored split by their producer (inference, 8 heads, fp32 state)
 bool rel_split_enabled();
 int launch_global_attn_h3(const float* img, const int32_t* segptr, const int32_t* src, const float* rel, const float* q, const float* kn,
@@ -117,8 +113,6 @@ int launch_global_attn_sc(const float* img, const int32_t* segptr, const int32_t
 bool gattn_f32mm_enabled();
 int launch_global_attn_mf(const float* img, const int32_t* segptr, const int32_t* src, const float* rel, const float* q, const float* kn,
                           const float* vn, int64_t N, float* agg, float* stats, const DropArg& drop, hipStream_t st);
-int launch_global_attn_mm(const float* img, const int32_t* segptr, const int32_t* src, const float* rel, const float* q, const float* kn,
-                          const float* vn, int64_t N, float* agg, hipStream_t st);
 // launch the instantiation selected by (heads, bf16 state storage, dropout)
 #define TS_GLOBAL_ATTN(heads, bf16, drop, ...)                                                                       \
   do {                                                                                                              \
@@ -147,11 +141,7 @@ int launch_global_attn_mm(const float* img, const int32_t* segptr, const int32_t
     }                                                                                                               \
   } while (0)
 __global__ void k_seg_merge(const int32_t* segptr, const float* rec, EdgeCount ec, int C, int64_t R, float* agg, float* stats, int heads,
-                            const float* img, const float* q, int add_cv, int rec_layout);
-// the fused edge attention on 32x32x16 matrix tiles (edge32.hip): same arguments, records in layout 1
-template <bool DROP, bool SAVE, bool PP>
-__global__ void k_edge_attn3(const float* img, const float* geom, const int32_t* dst, const float* q, EdgeCount ec, int C, float* rec, int heads,
-                             const int32_t* segptr, DropArg drop, float* emb_out);
+                            const float* img, const float* q, int add_cv);
 template <bool X6>
 __global__ void k_edge_embed(const float* img, const float* geom, EdgeCount ec, float* emb_out, int st_bf16);
 bool rel_embed_fused();

@@ -21,21 +21,24 @@ static int fused_threads() {                 // TRAJSDE_FUSED_THREADS=256: one w
   static const int t = [] { const char* e = getenv("TRAJSDE_FUSED_THREADS"); const int v = e ? atoi(e) : 512; return v == 256 ? 256 : 512; }();
   return t;
 }   // 2 waves per SIMD: ~220 VGPRs, weight image + 8 x 8 KB of parked query rows = 150 KB of LDS
-// TRAJSDE_EDGE_TILE=32: the fused edge attention on 32x32x16 matrix tiles (edge32.hip) -- half the matrix instructions and 12 %
-// fewer vector instructions, parity-tested, and 5 % slower un-profiled (0.839 against 0.800 ms on one box): the default stays
-// the 16x16x32 form.  TRAJSDE_EDGE_PINGPONG=1 adds its phase barriers that keep the second wave of a SIMD one phase behind the
-// first (edge32.hip phase_sync): slower still, kept as the record of the experiment.
-// TRAJSDE_FUSED_TILES=1: the inference instantiation with one tile per wave and 16 waves per workgroup (4 waves per SIMD, 116
-// VGPRs, weight fragments not shared between tiles): bit-identical, and within the noise of the default (0.85 vs 0.86-0.91 ms)
 // TRAJSDE_MERGE_KERNEL=1: the records are merged by k_seg_merge into agg rows (always so in training) instead of inside k_node_update
 static bool merge_in_update() { static const bool v = []() { const char* e = getenv("TRAJSDE_MERGE_KERNEL"); return !(e && atoi(e) != 0); }(); return v; }
-// TRAJSDE_EDGE_PIPE=1: the software-pipelined form of the fused edge attention (k_edge_attn2p: the wave's two tiles one stage apart,
-// vector work issued between the other tile's matrix instructions; bit-identical) for inference.  Measured slower than the lockstep
-// form (0.87 against 0.81 ms per launch; one wave per SIMD 1.12 against 0.98) -- HISTORY.md section 5 -- so it is an alternative.
-static bool edge_pipe() { static const bool v = []() { const char* e = getenv("TRAJSDE_EDGE_PIPE"); return e && atoi(e) == 1; }(); return v; }
-static bool fused_one_tile() { static const bool v = []() { const char* e = getenv("TRAJSDE_FUSED_TILES"); return e && atoi(e) == 1; }(); return v; }
-static bool edge_pingpong() { static const bool v = []() { const char* e = getenv("TRAJSDE_EDGE_PINGPONG"); return e && atoi(e) != 0; }(); return v; }
-static bool edge_tile32() { static const bool v = []() { const char* e = getenv("TRAJSDE_EDGE_TILE"); return e && atoi(e) == 32; }(); return v && TSDE_SPLIT_H3; }
+// Switches that selected a kernel form since removed, with the value that did (INTEGRATION.md "Retired switches"; their
+// measurements: HISTORY.md section 5).  Asking for one is refused at the entry points, not served by the default form.
+int refuse_retired_switches() {
+  struct Retired { const char* name; int value; };           // value 0: any value but 0
+  static const Retired table[] = {{"TRAJSDE_EDGE_TILE", 32}, {"TRAJSDE_EDGE_PIPE", 1}, {"TRAJSDE_FUSED_TILES", 1},
+                                  {"TRAJSDE_GATTN_MM", 0},   {"TRAJSDE_GMF_TILES", 2}, {"TRAJSDE_BRANCH_FUSED", 1}};
+  static const char* const asked = []() -> const char* {
+    for (const Retired& r : table) {
+      const char* e = getenv(r.name);
+      if (e && (r.value ? atoi(e) == r.value : atoi(e) != 0)) return r.name;
+    }
+    return nullptr;
+  }();
+  if (asked) return fail(TRAJSDE_ERR_UNSUPPORTED, std::string(asked) + " selects a kernel form that was removed from the library: unset it");
+  return TRAJSDE_OK;
+}
 static bool global_fused_env() { static const bool v = []() { const char* e = getenv("TRAJSDE_GLOBAL_UNFUSED"); return !(e && atoi(e) != 0); }(); return v; }
 static int fused_streams() { return 256 * 256; }             // a workgroup walks 256 streams (8 waves x 2 tiles or 4 waves x 4 tiles), one workgroup per CU
 static AttnPlan fused_plan(int64_t E) { return attn_plan(E, fused_streams()); }
@@ -140,58 +143,33 @@ int fused_edge_attention(const char* tag, bool dominant, const float* img, const
     const int threads = fused_threads();
     // a bounded list: enough waves for the most streams any E' <= E cuts into; the ones beyond the true count leave at once
     const int64_t streams = ec.dev ? std::min<int64_t>(E, fused_streams()) : pl.nstreams;
-    const int per_wg = (fused_one_tile() ? 1024 : threads) / 64 * (fused_one_tile() ? 16 : 32);      // streams a workgroup walks (256 by default)
+    const int per_wg = threads / 64 * 32;                                    // streams a workgroup walks (256 by default)
     const int grid = xcd_grid((streams + per_wg - 1) / per_wg);
     const int lds = (EdgeL6F::LDS_SIZE + 256 * 64) * 4;                      // weight image + the parked query rows of 256 streams (64 KB)
     const bool d = drop.p > 0.f, sv = emb_out != nullptr;
 #define TS_EA2H(N_, D_, S_, L_, H_) TS_LAUNCH_TAG(tag, dominant, (k_edge_attn2<N_, D_, S_, L_, H_>), grid, threads, lds, st, img, geom, dst, q, ec, pl.C, rec, heads, segptr, drop, emb_out)
 #define TS_EA2L(N_, D_, S_, L_) do { if (heads == 8) TS_EA2H(N_, D_, S_, L_, true); else TS_EA2H(N_, D_, S_, L_, false); } while (0)
 #define TS_EA2(N_, D_, S_) do { if (dominant) TS_EA2L(N_, D_, S_, 0); else TS_EA2L(N_, D_, S_, 1); } while (0)
-#define TS_EA3(D_, S_) if (edge_pingpong()) TS_LAUNCH_TAG(tag, dominant, (k_edge_attn3<D_, S_, true>), grid, threads, lds, st, img + EdgeL6F::SIZE, geom, dst, q, ec, pl.C, rec, heads, segptr, drop, emb_out); else TS_LAUNCH_TAG(tag, dominant, (k_edge_attn3<D_, S_, false>), grid, threads, lds, st, img + EdgeL6F::SIZE, geom, dst, q, ec, pl.C, rec, heads, segptr, drop, emb_out)
 #if !TSDE_SPLIT_H3
     (void)grid; (void)lds; (void)threads;
     return fail(TRAJSDE_ERR_UNSUPPORTED, "the fused edge attention (and with it the training forward) exists in the fp16x3 build only");
 #else
-#ifdef TSDE_PRODUCT
-    // the product library carries the default form only; a switch that asks for an alternative one is refused, not ignored
-    TS_REQUIRE(!edge_tile32() && !edge_pipe() && !fused_one_tile(),
-               "TRAJSDE_EDGE_TILE / TRAJSDE_EDGE_PIPE / TRAJSDE_FUSED_TILES select alternative kernel forms that live in "
-               "trajsde_amd/variants/libtrajsde_alt.so: point TRAJSDE_LIB at it");
-    {
-#else
-    if (edge_tile32()) {
-#if TSDE_SPLIT_H3
-      if (d && sv) TS_EA3(true, true);
-      else if (d) TS_EA3(true, false);
-      else if (sv) TS_EA3(false, true);
-      else TS_EA3(false, false);
-#endif
-    } else if (edge_pipe() && !d && !sv && !fused_one_tile()) {
-      // inference: the two tiles of a wave one stage apart, vector work issued between the other tile's matrix instructions
-      if (dominant) TS_LAUNCH_TAG(tag, dominant, (k_edge_attn2p<0>), grid, threads, lds, st, img, geom, dst, q, ec, pl.C, rec, heads);
-      else TS_LAUNCH_TAG(tag, dominant, (k_edge_attn2p<1>), grid, threads, lds, st, img, geom, dst, q, ec, pl.C, rec, heads);
-    } else if (fused_one_tile() && !d && !sv) {
-      if (dominant) TS_LAUNCH_TAG(tag, dominant, (k_edge_attn2<1, false, false, 0, false>), grid, 1024, lds, st, img, geom, dst, q, ec, pl.C, rec, heads, segptr, drop, emb_out);
-      else TS_LAUNCH_TAG(tag, dominant, (k_edge_attn2<1, false, false, 1, false>), grid, 1024, lds, st, img, geom, dst, q, ec, pl.C, rec, heads, segptr, drop, emb_out);
-    } else {
-#endif
-      if (d && sv) TS_EA2(2, true, true);
-      else if (d) TS_EA2(2, true, false);
-      else if (sv) TS_EA2(2, false, true);
-      else TS_EA2(2, false, false);
-    }
+    if (d && sv) TS_EA2(2, true, true);
+    else if (d) TS_EA2(2, true, false);
+    else if (sv) TS_EA2(2, false, true);
+    else TS_EA2(2, false, false);
 #endif   // TSDE_SPLIT_H3
 #undef TS_EA2
 #undef TS_EA2L
-#undef TS_EA3
+#undef TS_EA2H
   }
-  // inference with the default record layout: the consumer of the aggregate (k_node_update) merges the records itself
-  if (defer != nullptr && stats == nullptr && emb_out == nullptr && drop.p == 0.f && !edge_tile32() && merge_in_update()) {
+  // inference: the consumer of the aggregate (k_node_update) merges the records itself
+  if (defer != nullptr && stats == nullptr && emb_out == nullptr && drop.p == 0.f && merge_in_update()) {
     *defer = SegMerge{rec, segptr, ec, pl.C, img + EdgeL6F::CV};
     return TRAJSDE_OK;
   }
   if (defer != nullptr) *defer = no_merge();
-  TS_LAUNCH(k_seg_merge, cdiv(R, 4), 256, 0, st, segptr, rec, ec, pl.C, R, agg, stats, heads, img, q, drop.p > 0.f ? 0 : 1, edge_tile32() ? 1 : 0);
+  TS_LAUNCH(k_seg_merge, cdiv(R, 4), 256, 0, st, segptr, rec, ec, pl.C, R, agg, stats, heads, img, q, drop.p > 0.f ? 0 : 1);
   return TRAJSDE_OK;
 }
 bool attn_fused_enabled() { return attn_fused(); }
@@ -331,6 +309,7 @@ int trajsde_encoder_forward(const trajsde_batch* b, const trajsde_graph* g, cons
                             const float* step_tab /*HOST [H,8]*/, const trajsde_noise* noise, void* ws, int64_t ws_bytes,
                             float* local_embed, float* diff_pick, float* aa_out_user, float* latent_ys, const trajsde_dropout* dropout,
                             void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob && step_tab && ws && local_embed && diff_pick, "encoder_forward: null pointer");
   TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), "encoder_forward: dropout p must be in [0, 1)");
   const DropArg drop_aa = dropout ? make_drop(dropout->p, dropout->seed, 0) : no_drop();     // block ids of dropout.hpp
@@ -369,6 +348,7 @@ int64_t trajsde_encoder_ood_ws_bytes(const trajsde_batch* b, const trajsde_graph
 int trajsde_encoder_forward_ood(const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob,
                                 const float* step_tab /*HOST [H,8]*/, const trajsde_noise* noise, int n_samples, void* ws,
                                 int64_t ws_bytes, float* local_embed, float* stds, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob && step_tab && ws && local_embed && stds, "encoder_forward_ood: null pointer");
   TS_REQUIRE(g->aa_dst && g->la_dst && g->orig, "encoder_forward_ood: graph not compacted");
   TS_REQUIRE(g->exact || (attn_fused() && g->counts), "encoder_forward_ood: a graph from trajsde_graph_prepare_async needs the fused edge attention");
@@ -412,6 +392,7 @@ int trajsde_encoder_grid_forward(const trajsde_batch* b, const trajsde_graph* g,
 int trajsde_encoder_grid_forward_train(const trajsde_batch* b, const trajsde_graph* g, const float* rot, const float* blob, int num_heads,
                                        int num_temporal_layers, void* ws, int64_t ws_bytes, float* local_embed,
                                        const trajsde_dropout* dropout, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && rot && blob && ws && local_embed, "encoder_grid_forward: null pointer");
   TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), "encoder_grid_forward: dropout p must be in [0, 1)");
   const bool dropping = dropout && dropout->p > 0.f;
@@ -466,7 +447,7 @@ int trajsde_aggregator_forward(const trajsde_batch* b, const trajsde_graph* g, c
 // readers are the split-image attention (gattn_h3.hip): 8 heads, fp32 state, no dropout, the default kernel forms.
 static bool rel_split_possible() {
 #if TSDE_SPLIT_H3
-  return rel_split_enabled() && !state_bf16() && edge_x6() && rel_embed_fused() && global_fused_env() && !gattn_mm_enabled();
+  return rel_split_enabled() && !state_bf16() && edge_x6() && rel_embed_fused() && global_fused_env();
 #else
   return false;
 #endif
@@ -496,6 +477,7 @@ int trajsde_encoder_fork_stream(void* side_stream) {
 }
 
 int trajsde_aggregator_prepare(const trajsde_batch* b, const trajsde_graph* g, const float* blob, void* ws, int64_t ws_bytes, void* stream_) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && blob && ws, "aggregator_prepare: null pointer");
   TS_REQUIRE(g->g_src && g->g_segptr, "aggregator_prepare: graph not compacted (call trajsde_graph_compact)");
   AggWs w(b, g, ws, ws_bytes);
@@ -523,6 +505,7 @@ int trajsde_aggregator_forward_prepared(const trajsde_batch* b, const trajsde_gr
 static int aggregator_forward_impl(const trajsde_batch* b, const trajsde_graph* g, const float* blob, int num_layers, int num_modes,
                                    int num_heads, const float* local_embed, void* ws, int64_t ws_bytes, float* global_embed,
                                    const trajsde_dropout* dropout, void* stream_, bool rel_ready) {
+  if (int rc = refuse_retired_switches()) return rc;
   TS_REQUIRE(b && g && blob && local_embed && ws && global_embed, "aggregator_forward: null pointer");
   TS_REQUIRE(!dropout || (dropout->p >= 0.f && dropout->p < 1.f), "aggregator_forward: dropout p must be in [0, 1)");
   TS_REQUIRE(num_heads == 8 || num_heads == 4, "aggregator_forward: num_heads must be 8 or 4");
@@ -564,8 +547,6 @@ static int aggregator_forward_impl(const trajsde_batch* b, const trajsde_graph* 
           return rc;
       } else if (split) {
         if (int rc = launch_global_attn_h3(lb + AggLayerL::ATTN, g->g_segptr, g->g_src, w.rel, w.q, w.kn, w.vn, N, w.agg, st)) return rc;
-      } else if (num_heads == 8 && !state_bf16() && drop.p == 0.f && gattn_mm_enabled()) {
-        if (int rc = launch_global_attn_mm(lb + AggLayerL::ATTN, g->g_segptr, g->g_src, w.rel, w.q, w.kn, w.vn, N, w.agg, st)) return rc;
       } else if (num_heads == 8 && !state_bf16() && gattn_f32mm_enabled() && E > 0) {
         if (int rc = launch_global_attn_mf(lb + AggLayerL::ATTN, g->g_segptr, g->g_src, w.rel, w.q, w.kn, w.vn, N, w.agg, nullptr, drop, st)) return rc;
       } else {
