@@ -188,6 +188,12 @@ ENC_COT_EXT_SIGNATURES = {
     "trajsde_encoder_cotangent_backward": (C.c_int, [C.POINTER(Batch), C.POINTER(Graph), P, P, P, P, P, C.POINTER(Noise), P, P, P, P, I64,
                                                      C.POINTER(P), C.c_int, P, P, C.POINTER(Dropout), C.c_int, P, I64, P]),
 }
+# include/trajsde_hip_capacity.h: a batch staged into capacity-sized static buffers with inert padding (csrc/pad.hip;
+# runtime.CapacityBuffers); a table of its own too
+CAPACITY_EXT_SIGNATURES = {
+    "trajsde_batch_pad_fits": (I32, [C.POINTER(Batch), C.POINTER(Batch)]),
+    "trajsde_batch_pad": (I32, [C.POINTER(Batch), P, I32, C.POINTER(Batch), P, C.c_int, F32, P, P, P, P]),
+}
 # the reduction's geometry (csrc/clip.hip; the workspace query returns 8 bytes per workgroup, which ties these to the library):
 # a workgroup takes CLIP_WG_FLOATS consecutive elements a pass, the grid is at most CLIP_MAX_WGS workgroups and strides beyond that
 CLIP_WG_FLOATS, CLIP_MAX_WGS = 2048, 512
@@ -205,7 +211,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **COT_SEL_EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES,
-                                   **ENC_COT_EXT_SIGNATURES}.items():
+                                   **ENC_COT_EXT_SIGNATURES, **CAPACITY_EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

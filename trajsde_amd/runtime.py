@@ -1473,3 +1473,253 @@ class GraphContext:
         if exact:
             gc.make_exact()
         return gc
+
+
+# ---------------------------------------------------------------------------------------------------- one shape for any batch that fits
+@dataclass(frozen=True)
+class BatchCapacity:
+    """The largest batch a set of CapacityBuffers takes: actors, scenes (= target agents), columns of `edge_index`, lane segments, columns
+    of `lane_actor_index`.  The static buffers hold this plus a permanent reserve of one scene, two actors and one lane
+    (`padded_sizes()`), so that pad edges always have inert endpoints -- also for a batch that fills the capacity.  Every scene
+    slot a batch leaves empty is a pad scene of one pad actor (the number of fake agents is part of the static shape), hence the rule
+    `N + (scenes - S) <= actors` of `fits()`."""
+    actors: int
+    scenes: int
+    edges: int
+    lanes: int
+    lane_edges: int
+
+    RESERVE_ACTORS, RESERVE_SCENES, RESERVE_LANES = 2, 1, 1
+
+    def __post_init__(self) -> None:
+        if self.actors < 1 or self.scenes < 1 or min(self.edges, self.lanes, self.lane_edges) < 0:
+            raise ValueError(f"{self}: a capacity holds at least one actor and one scene, and no negative size")
+        if self.actors < self.scenes:
+            raise ValueError(f"{self}: every scene holds an actor -- fewer actors than scenes fit no batch")
+
+    @staticmethod
+    def sizes_of(batch) -> Dict[str, int]:
+        """{actors, scenes, edges, lanes, lane_edges} of a batch, from shapes alone (any device, no synchronisation)"""
+        return {"actors": int(batch["x"].shape[0]), "scenes": int(batch["agent_index"].numel()), "edges": int(batch["edge_index"].shape[1]),
+                "lanes": int(batch["lane_positions"].shape[0]), "lane_edges": int(batch["lane_actor_index"].shape[1])}
+
+    @classmethod
+    def covering(cls, batches) -> "BatchCapacity":
+        """the smallest capacity every one of `batches` (batch objects, or dicts as `sizes_of` returns them) fits: one host pass over sizes"""
+        sizes = [b if isinstance(b, dict) else cls.sizes_of(b) for b in batches]
+        if not sizes:
+            raise ValueError("BatchCapacity.covering needs at least one batch")
+        scenes = max(s["scenes"] for s in sizes)
+        return cls(actors=max(s["actors"] + scenes - s["scenes"] for s in sizes), scenes=scenes, edges=max(s["edges"] for s in sizes),
+                   lanes=max(s["lanes"] for s in sizes), lane_edges=max(s["lane_edges"] for s in sizes))
+
+    def why_not(self, batch) -> Optional[str]:
+        """None when the batch fits, else a message that names the first overflowing dimension"""
+        s = batch if isinstance(batch, dict) else self.sizes_of(batch)
+        if s["scenes"] < 1 or s["actors"] < 1:
+            return "an empty batch (no scene or no actor)"
+        if s["scenes"] > self.scenes:
+            return f"scenes: {s['scenes']} exceed the capacity of {self.scenes}"
+        if s["actors"] + (self.scenes - s["scenes"]) > self.actors:
+            return (f"actors: {s['actors']} plus one for each of the {self.scenes - s['scenes']} pad scenes exceed the capacity of "
+                    f"{self.actors}")
+        for dim in ("edges", "lanes", "lane_edges"):
+            if s[dim] > getattr(self, dim):
+                return f"{dim}: {s[dim]} exceed the capacity of {getattr(self, dim)}"
+        return None
+
+    def fits(self, batch) -> bool:
+        return self.why_not(batch) is None
+
+    def padded_sizes(self) -> Tuple[int, int, int, int, int]:
+        """(N, A, E, L, E_al) of the static buffers: the capacity plus the reserve"""
+        return (self.actors + self.RESERVE_ACTORS, self.scenes + self.RESERVE_SCENES, self.edges, self.lanes + self.RESERVE_LANES,
+                self.lane_edges)
+
+
+PAD_FAR_RADII = 200.0          # a pad lane-actor vector is (200 r, 200 r) for local_radius r (csrc/pad.hip): the radius filter drops it
+
+
+def pad_batch_host(batch, capacity: BatchCapacity, num_modes: int, local_radius: Optional[float] = None):
+    """The torch twin of trajsde_batch_pad (include/trajsde_hip_capacity.h), on the tensors' own device (meant for the host: it is the
+    launch's oracle and the input of the CPU oracle test): -> (the padded batch, {"fake_row_ids", "enc_row_ids", "dec_row_ids"}).
+    Masks come out as bool, floats as float32, indices as int64, row ids as int32.  A batch of zero actors and zero scenes is
+    accepted (the all-padding state CapacityBuffers start in)."""
+    from trajsde_amd.data import TemporalData
+    why = None if int(batch["x"].shape[0]) == 0 and int(batch["agent_index"].numel()) == 0 else capacity.why_not(batch)
+    if why is not None:
+        raise _lib.TrajsdeError(f"the batch does not fit the capacity -- {why}")
+    radius = GraphContext.DEFAULT_RADIUS if local_radius is None else float(local_radius)
+    far = PAD_FAR_RADII * radius if radius > 0 else 0.0
+    Np, Ap, Ep, Lp, Eap = capacity.padded_sizes()
+    x = batch["x"]
+    dev = x.device
+    N, S, K = int(x.shape[0]), int(batch["agent_index"].numel()), int(num_modes)
+    E, L, Ea = int(batch["edge_index"].shape[1]), int(batch["lane_positions"].shape[0]), int(batch["lane_actor_index"].shape[1])
+    pad_scenes = Ap - S
+    base = N + pad_scenes - 1                                   # first actor of the permanent pad scene
+    M = Np - base                                               # its actors: >= 2
+    i64 = dict(dtype=torch.int64, device=dev)
+
+    def rows(t, n, fill, dtype):
+        t = t.to(dtype)
+        out = torch.full((n,) + tuple(t.shape[1:]), fill, dtype=dtype, device=dev)
+        out[:t.shape[0]] = t
+        return out
+
+    out = {"x": rows(x, Np, 0.0, torch.float32), "positions": rows(batch["positions"], Np, 0.0, torch.float32),
+           "padding_mask": rows(batch["padding_mask"], Np, True, torch.bool), "bos_mask": rows(batch["bos_mask"], Np, False, torch.bool),
+           "rotate_angles": rows(batch["rotate_angles"], Np, 0.0, torch.float32),
+           "lane_positions": rows(batch["lane_positions"], Lp, 0.0, torch.float32),
+           "lane_paddings": rows(batch["lane_paddings"], Lp, 0.0, torch.float32),
+           "lane_actor_vectors": rows(batch["lane_actor_vectors"], Eap, far, torch.float32)}
+    if batch.y is not None:
+        out["y"] = rows(batch.y, Np, 0.0, torch.float32)
+    j = torch.arange(Ep - E, **i64)
+    d = j % M
+    s = (d + 1 + (j // M) % (M - 1)) % M
+    out["edge_index"] = torch.cat([batch["edge_index"].to(torch.int64), torch.stack([base + s, base + d])], dim=1)
+    out["agent_index"] = torch.cat([batch["agent_index"].to(torch.int64).reshape(-1), N + torch.arange(pad_scenes, **i64)])
+    out["batch"] = torch.cat([batch["batch"].to(torch.int64), S + torch.arange(Np - N, **i64).clamp(max=pad_scenes - 1)])
+    out["source"] = torch.cat([batch["source"].to(torch.int64).reshape(-1), torch.zeros(pad_scenes, **i64)])
+    j = torch.arange(Eap - Ea, **i64)
+    out["lane_actor_index"] = torch.cat([batch["lane_actor_index"].to(torch.int64), torch.stack([torch.full_like(j, Lp - 1), base + j % M])], dim=1)
+    out["num_nodes"] = Np
+    i = torch.arange(Np + Ap, **i64)
+    enc = torch.where(i < N, i, torch.where(i < Np, i + S, torch.where(i - Np < S, N + (i - Np), i)))
+    n = torch.arange(Np, **i64)
+    k = torch.arange(K, **i64)[:, None]
+    dec = torch.where(n[None, :] < N, k * N + n[None, :], K * N + k * (Np - N) + (n[None, :] - N))
+    ids = {"fake_row_ids": torch.arange(Ap, dtype=torch.int32, device=dev), "enc_row_ids": enc.to(torch.int32),
+           "dec_row_ids": dec.reshape(-1).to(torch.int32)}
+    return TemporalData(**out), ids
+
+
+def _empty_batch(H: int, TT: int, lane_pts: int):
+    """a batch of no actor and no scene: pad_batch_host of it is the all-padding state"""
+    from trajsde_amd.data import TemporalData
+    z = torch.zeros
+    return TemporalData(x=z(0, H, 2), positions=z(0, TT, 2), padding_mask=z(0, TT, dtype=torch.bool), bos_mask=z(0, H, dtype=torch.bool),
+                        rotate_angles=z(0), edge_index=z(2, 0, dtype=torch.int64), agent_index=z(0, dtype=torch.int64),
+                        batch=z(0, dtype=torch.int64), source=z(0, dtype=torch.int64), lane_positions=z(0, lane_pts, 2),
+                        lane_paddings=z(0, lane_pts), lane_actor_index=z(2, 0, dtype=torch.int64), lane_actor_vectors=z(0, 2),
+                        y=z(0, TT - H, 2))
+
+
+def _c_batch(data, n_agents: Optional[int] = None, keep: Optional[list] = None) -> "_lib.Batch":
+    """the C struct over a batch's device tensors, in the dtypes the kernels read (float32 / bytes / int64: converted copies where a
+    tensor has another, kept alive in `keep`)"""
+    keep = [] if keep is None else keep
+
+    def ptr(t, dtype):
+        if dtype is torch.uint8:
+            t = t.contiguous()
+            t = t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)
+        else:
+            t = t.to(dtype).contiguous()
+        keep.append(t)
+        return t.data_ptr() if t.numel() else None
+
+    f, u, i = torch.float32, torch.uint8, torch.int64
+    lp, ei, lai = data["lane_positions"], data["edge_index"], data["lane_actor_index"]
+    return _lib.Batch(data["x"].shape[0], data["agent_index"].numel() if n_agents is None else n_agents, ei.shape[1], lp.shape[0], lai.shape[1],
+                      data["x"].shape[1], data["positions"].shape[1], lp.shape[1] if lp.dim() > 1 else 0,
+                      ptr(data["x"], f), ptr(data["positions"], f), ptr(data["padding_mask"], u), ptr(data["bos_mask"], u),
+                      ptr(data["rotate_angles"], f), ptr(ei, i), ptr(data["agent_index"], i), ptr(data["batch"], i), ptr(data["source"], i),
+                      ptr(lp, f), ptr(data["lane_paddings"], f), ptr(lai, i), ptr(data["lane_actor_vectors"], f))
+
+
+class CapacityBuffers:
+    """Capacity-sized static batch tensors and row-id tables on a device, filled by ONE launch per batch (trajsde_batch_pad, csrc/pad.hip):
+
+        buf = CapacityBuffers(BatchCapacity.covering(batches), num_modes=K, device=dev, time_slots=21 + F)
+        buf.stage(batch)                                    # any batch that fits: same shapes, same addresses, inert padding
+        out = model(buf.batch, noise=buf.noise(seed))       # real rows: model(batch, noise=NoiseSpec(seed=seed)), see pad_batch_host
+
+    `buf.batch` keeps its tensors' shapes and addresses over every `stage()`; `buf.noise(seed)` keys the three noise streams by the
+    row-id tables, so the real rows (`[:N]` of loc / pi / reg_mask, `[:S]` of diff_in / diff_out) draw the noise of the unpadded
+    batch.  Every call overwrites every element of every tensor and table: a smaller batch after a larger one leaves nothing behind.
+    Refused with a message: a host tensor or one on another device among the batch's, a batch that does not fit (`why_not`), other
+    time slots or points per lane.
+    The forward REBINDS `buf.batch.y` to its rotated copy (MODEL:83-84): `stage()` puts the static tensor back."""
+
+    def __init__(self, capacity: BatchCapacity, num_modes: int, device, time_slots: int, history_steps: int = 21, lane_points: int = 10,
+                 local_radius: Optional[float] = None) -> None:
+        if not isinstance(capacity, BatchCapacity):
+            raise TypeError("capacity must be a runtime.BatchCapacity")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TrajsdeError("CapacityBuffers must live on the GPU: the staging launch has no CPU implementation "
+                                    "(runtime.pad_batch_host is its torch twin)")
+        if self.device.index is None:                     # ("cuda": the current device, spelled out -- stage() compares devices)
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.capacity, self.num_modes = capacity, int(num_modes)
+        self.H, self.TT, self.lane_pts = int(history_steps), int(time_slots), int(lane_points)
+        self.F = self.TT - self.H
+        if self.F < 1:
+            raise _lib.TrajsdeError(f"CapacityBuffers: time_slots {self.TT} leave no future step behind the {self.H} history steps")
+        self.radius = GraphContext.DEFAULT_RADIUS if local_radius is None else float(local_radius)
+        # the all-padding state (the host twin's, copied over once)
+        empty, ids = pad_batch_host(_empty_batch(self.H, self.TT, self.lane_pts), capacity, self.num_modes, self.radius)
+        self.batch = empty.to(self.device)
+        self._y = self.batch.y
+        self.ids = {k: v.to(self.device) for k, v in ids.items()}
+        keep = []
+        self._dst = _c_batch(self.batch, keep=keep)
+        # the launch writes through these addresses on every stage(): each must be the static tensor's own, not a converted copy's
+        held = {t.data_ptr() for t in keep if t.numel()}
+        own = {v.data_ptr() for v in self.batch.as_dict().values() if torch.is_tensor(v) and v.numel()}
+        if not held <= own:
+            raise _lib.TrajsdeError("CapacityBuffers: a static tensor is not in the dtype / layout the launch writes (internal error)")
+
+    def why_not(self, batch) -> Optional[str]:
+        """None when `batch` can be staged, else a message that names what does not fit"""
+        why = self.capacity.why_not(batch)
+        if why is None and int(batch["x"].shape[1]) != self.H:
+            why = f"history steps: {int(batch['x'].shape[1])}, the buffers have {self.H}"
+        if why is None and int(batch["positions"].shape[1]) != self.TT:
+            why = f"time slots of positions / padding_mask: {int(batch['positions'].shape[1])}, the buffers have {self.TT}"
+        lp = batch["lane_positions"]
+        if why is None and lp.shape[0] > 0 and int(lp.shape[1]) != self.lane_pts:
+            why = f"points per lane: {int(lp.shape[1])}, the buffers have {self.lane_pts}"
+        y = batch.y
+        if why is None and y is not None and tuple(y.shape) != (int(batch["x"].shape[0]), self.F, 2):
+            why = f"targets y {tuple(y.shape)}, the buffers have [N,{self.F},2]"
+        return why
+
+    def fits(self, batch) -> bool:
+        return self.why_not(batch) is None
+
+    def stage(self, batch) -> None:
+        """`batch` (device tensors) into the static tensors and the row-id tables: one launch on the current stream"""
+        for k in ("x", "positions", "padding_mask", "bos_mask", "rotate_angles", "edge_index", "agent_index", "batch", "source",
+                  "lane_positions", "lane_paddings", "lane_actor_index", "lane_actor_vectors", "y"):
+            t = batch[k]
+            if t is None:                                 # (only `y` may be absent)
+                continue
+            _require_gpu(t, f"data['{k}']")
+            if t.device != self.device:
+                raise _lib.TrajsdeError(f"data['{k}'] lives on {t.device}, these buffers on {self.device}: the staging launch reads and "
+                                        "writes one device")
+        why = self.why_not(batch)
+        if why is not None:
+            raise _lib.TrajsdeError(f"the batch does not fit these buffers ({self.capacity}) -- {why}")
+        keep = []
+        src = _c_batch(batch, keep=keep)
+        src.lane_pts = self.lane_pts                      # (a batch without lanes: an empty lane tensor of any second dimension)
+        y = batch.y
+        if y is not None:
+            y = y.to(torch.float32).contiguous()
+        ids = self.ids
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().trajsde_batch_pad(C.byref(src), _ptr(y), self.F, C.byref(self._dst), self._y.data_ptr(), self.num_modes,
+                                                    self.radius, ids["fake_row_ids"].data_ptr(), ids["enc_row_ids"].data_ptr(),
+                                                    ids["dec_row_ids"].data_ptr(), _stream()), "trajsde_batch_pad")
+        self.batch.y = self._y
+        if GraphContext.KEY in self.batch:                # the launch writes in place: no version counter moves, so the graph a forward
+            del self.batch[GraphContext.KEY]              # parked on the buffers would pass for current -- the next forward builds its own
+
+    def noise(self, seed: int) -> NoiseSpec:
+        """NoiseSpec(seed) keyed by the row-id tables of the batch staged last"""
+        return NoiseSpec(seed=int(seed), fake_row_ids=self.ids["fake_row_ids"], enc_row_ids=self.ids["enc_row_ids"],
+                         dec_row_ids=self.ids["dec_row_ids"])
