@@ -194,6 +194,14 @@ CAPACITY_EXT_SIGNATURES = {
     "trajsde_batch_pad_fits": (I32, [C.POINTER(Batch), C.POINTER(Batch)]),
     "trajsde_batch_pad": (I32, [C.POINTER(Batch), P, I32, C.POINTER(Batch), P, C.c_int, F32, P, P, P, P]),
 }
+# include/trajsde_hip_mc.h: Monte-Carlo decoding, R sample paths per (mode, actor) in one launch with the statistics reduced on the
+# device (csrc/decoder_mc.hip; runtime.StageRuntime.decoder_forward_mc); a table of its own too
+MC_EXT_SIGNATURES = {
+    "trajsde_decoder_mc_ws_bytes": (I64, [I32, C.c_int, C.c_int, C.c_int]),
+    "trajsde_decoder_forward_mc": (I32, [I32, C.c_int, C.c_int, C.c_int, P, P, P, P, C.c_int, P, F32, C.POINTER(Noise), C.c_int, I64,
+                                             P, I64, P, P, P, P, P, P]),
+}
+MC_MAX_SAMPLES = 65536                                    # TRAJSDE_MC_MAX_SAMPLES
 # the reduction's geometry (csrc/clip.hip; the workspace query returns 8 bytes per workgroup, which ties these to the library):
 # a workgroup takes CLIP_WG_FLOATS consecutive elements a pass, the grid is at most CLIP_MAX_WGS workgroups and strides beyond that
 CLIP_WG_FLOATS, CLIP_MAX_WGS = 2048, 512
@@ -211,7 +219,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **COT_SEL_EXT_SIGNATURES, **GRID_EXT_SIGNATURES, **CLIP_EXT_SIGNATURES,
-                                   **ENC_COT_EXT_SIGNATURES, **CAPACITY_EXT_SIGNATURES}.items():
+                                   **ENC_COT_EXT_SIGNATURES, **CAPACITY_EXT_SIGNATURES, **MC_EXT_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError here = header/library mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         if handle.trajsde_abi_version() != ABI_VERSION:

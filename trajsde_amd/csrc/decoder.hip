@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "decoder_shared.hpp"
 #include "layouts.hpp"
 #include "philox.hpp"
 #include "range.hpp"
@@ -26,35 +27,6 @@ TSDE_STAMP_TABLE(sde_step, 8)   // diagnostic builds (tools/phase_stamps.py): ph
 namespace tsde {
 #ifndef TSDE_STAMPS
 static unsigned long long* const g_stamps_sde_step = nullptr;
-#endif
-
-// Linear(64,64)-LN-ReLU-Linear(64,2) head on state s -> (o0, o1)
-__device__ __forceinline__ void head_eval(float& o0, float& o1, const f4 (&s)[4], const float* img, const Lane& L) {
-  f4 h[4];
-  linear<4, 4>(h, s, img + HeadL::W0, img + HeadL::B0, L);
-  layer_norm<4>(h, img + HeadL::G, img + HeadL::E, L.g);
-  relu<4>(h);
-  o0 = row_dot(h, img + HeadL::W3, L.g) + img[HeadL::B3];
-  o1 = row_dot(h, img + HeadL::W3 + 64, L.g) + img[HeadL::B3 + 1];
-}
-
-#if TSDE_SPLIT_H3
-// both heads of the fused kernel on one split of s: stacked first layers (HeadPairL6), fp16x3 matrix products
-__device__ __forceinline__ void head_pair_eval(float& lx, float& ly, float& sx, float& sy, const f4 (&s)[4], const float* img,
-                                               const Lane& L) {
-  using HP = HeadPairL6;
-  f4 h[8];
-  linear_x6<8, 4>(h, s, img + HP::W0, img + HP::B0, L);
-  f4 a[4] = {h[0], h[1], h[2], h[3]}, b[4] = {h[4], h[5], h[6], h[7]};
-  layer_norm<4>(a, img + HP::G_LOC, img + HP::E_LOC, L.g);
-  relu<4>(a);
-  lx = row_dot(a, img + HP::W3_LOC, L.g) + img[HP::B3_LOC];
-  ly = row_dot(a, img + HP::W3_LOC + 64, L.g) + img[HP::B3_LOC + 1];
-  layer_norm<4>(b, img + HP::G_SC, img + HP::E_SC, L.g);
-  relu<4>(b);
-  sx = row_dot(b, img + HP::W3_SC, L.g) + img[HP::B3_SC];
-  sy = row_dot(b, img + HP::W3_SC + 64, L.g) + img[HP::B3_SC + 1];
-}
 #endif
 
 __global__ __launch_bounds__(1024) void k_dec_init(const float* __restrict__ blob, const float* __restrict__ local,
@@ -382,15 +354,18 @@ int pick_grid(int64_t ntiles, int waves_per_wg) {
   return int(wgs < 1 ? 1 : (wgs > 256 ? 256 : wgs));   // one resident workgroup per CU (LDS-bound), grid-stride beyond
 }
 
+// y0 [K*N,64] (fp32 or bf16: trajsde_state_storage) and pi [N,K] of a decoder blob: the launch in front of every decode kernel
+int decoder_init(int32_t N, int num_modes, const float* blob, const float* local_embed, const float* global_embed, float* y0, float* pi,
+                 hipStream_t stream) {
+  const int64_t ntiles = (int64_t(N) * num_modes + 15) / 16;
+  TS_LAUNCH(k_dec_init, pick_grid(ntiles, 8), 512, DecInitL::SIZE * 4, stream, blob + DecBlob::INIT, local_embed, global_embed, N,
+            num_modes, y0, pi, state_bf16() ? 1 : 0);
+  return TRAJSDE_OK;
+}
+
 }  // namespace tsde
 
 using namespace tsde;
-
-static NoiseArg to_arg(const trajsde_noise* n) {
-  NoiseArg a{0, nullptr, nullptr};
-  if (n) { a.seed = n->seed; a.z = n->z; a.row_ids = n->row_ids; a.seed_dev = n->seed_dev; }
-  return a;
-}
 
 static int decoder_forward(bool milstein, int32_t N, int num_modes, int future_steps, const float* blob, const float* local_embed,
                            const float* global_embed, const float* step_table, int n_euler, const float* out_table,
@@ -404,8 +379,7 @@ static int decoder_forward(bool milstein, int32_t N, int num_modes, int future_s
   const int64_t rows = int64_t(N) * num_modes;
   float* y0 = cv.take<float>(rows * 64);
   const int64_t ntiles = (rows + 15) / 16;
-  TS_LAUNCH(k_dec_init, pick_grid(ntiles, 8), 512, DecInitL::SIZE * 4, stream, blob + DecBlob::INIT, local_embed, global_embed, N,
-            num_modes, y0, pi, state_bf16() ? 1 : 0);
+  if (const int rc = decoder_init(N, num_modes, blob, local_embed, global_embed, y0, pi, stream)) return rc;
   // 768 threads = 12 waves = 3 per SIMD (168 VGPRs each); 256 CUs x 12 waves = 3072 path tiles in flight
   static const int dthreads = []() { const char* v = getenv("TRAJSDE_THREADS_DECODE"); const int t = v ? atoi(v) : 768; return (t >= 64 && t <= 768 && t % 64 == 0) ? t : 768; }();
   static const bool x6 = []() { const char* e = getenv("TRAJSDE_DECODE_FP32"); return !(e && atoi(e) != 0); }();

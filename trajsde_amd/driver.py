@@ -47,14 +47,20 @@ def build_model(cfg: dict, ckpt: Optional[str] = None, device="cuda", init_seed:
 
 
 @torch.no_grad()
-def evaluate(model, batches: Iterable, seed: int = 0) -> dict:
-    """trainer.test(...): test_step per batch, then the epoch-end metric dump (MODEL:133-165)."""
+def evaluate(model, batches: Iterable, seed: int = 0, mc_samples: Optional[int] = None) -> dict:
+    """trainer.test(...): test_step per batch, then the epoch-end metric dump (MODEL:133-165).  `mc_samples` = R: every batch is
+    decoded with R draws of the decoder's noise (model.predict_samples) and the metrics are updated with the sample mean `loc_mean`
+    in place of the single draw `loc`; None: one draw, as before."""
+    if mc_samples is not None and not hasattr(model, "predict_samples"):
+        raise ValueError("mc_samples: this model's decoder is deterministic (no predict_samples)")
     for metric in model.metrics_vl:
         metric.reset()
     stochastic = "noise" in inspect.signature(model.forward).parameters      # the vanilla HiVT variant has no noise to seed
     rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
     for i, batch in enumerate(batches):
-        if seed is None or not stochastic:
+        if mc_samples is not None:
+            _mc_test_step(model, batch, i, None if seed is None else seed + i + RANK_SEED_STRIDE * rank, int(mc_samples))
+        elif seed is None or not stochastic:
             model.test_step(batch, i)
         else:
             _seeded_test_step(model, batch, i, seed + i + RANK_SEED_STRIDE * rank)
@@ -67,6 +73,17 @@ def _seeded_test_step(model, data, batch_idx, seed):
     output = model(data, noise=NoiseSpec(seed=seed))
     if data.y is not None:
         y_hat, y, mask, source = model._agent_eval_tensors(data, output)
+        for metric in model.metrics_vl:
+            metric.update(y_hat.detach(), y.detach(), mask.detach(), source.detach())
+    return output
+
+
+def _mc_test_step(model, data, batch_idx, seed, n_samples):
+    output = model.predict_samples(data, n_samples, noise=None if seed is None else NoiseSpec(seed=seed))
+    if data.y is not None:
+        view = dict(output)
+        view["loc"] = output["loc_mean"]
+        y_hat, y, mask, source = model._agent_eval_tensors(data, view)
         for metric in model.metrics_vl:
             metric.update(y_hat.detach(), y.detach(), mask.detach(), source.detach())
     return output
@@ -872,6 +889,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cotangent-support", "--cotangent_support", dest="cotangent_support", choices=("all", "winner"), default=None,
                     help="--train, loss sets on the cotangent route: replay all K * N decoder paths, or only each actor's one mode "
                          "with a non-zero dL/dloc (winner-takes-all losses on loc); absent: the YAML's cotangent_support (default all)")
+    ap.add_argument("--mc-samples", "--mc_samples", dest="mc_samples", type=int, default=None, metavar="R",
+                    help="evaluation: decode every batch with R >= 2 draws of the decoder's noise in one launch and score the sample "
+                         "mean (model.predict_samples); absent: one draw")
     return ap
 
 
@@ -924,7 +944,7 @@ def main() -> None:
         batches = datamodule_batches(cfg, dev, rank, world, args.nu_dir, args.argo_dir)
     else:
         batches = synthetic_batches(args.synthetic, args.batches, dev, rank, world)
-    res = evaluate(model, batches)                                                    # metric states all-reduce in compute(): every rank
+    res = evaluate(model, batches, mc_samples=args.mc_samples)                          # metric states all-reduce in compute(): every rank
     if rank == 0:
         text = json.dumps(res)
         print(text)                                                                   # first: nothing below can lose the numbers

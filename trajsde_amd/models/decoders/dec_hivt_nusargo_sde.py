@@ -66,3 +66,14 @@ class SDEDecoder(ParamTree):
         if stage_autograd.active(self, local_embed, global_embed):
             return stage_autograd.decoder(self, data, local_embed, global_embed, noise)
         return self._rt.decoder_forward(data, local_embed, global_embed, noise)
+
+    def sample(self, data, local_embed, global_embed, n_samples: int, noise: Optional["runtime.NoiseSpec"] = None,
+               sample_stride: Optional[int] = None, return_samples: bool = False):
+        """Monte-Carlo decoding: `n_samples` sample paths of every (mode, actor) from these embeddings in one launch, reduced on the
+        device -> {'loc' (sample 0: what forward() returns under the same noise), 'pi', 'reg_mask', 'loc_mean', 'loc_cov'[, 'samples']}
+        (runtime.StageRuntime.decoder_forward_mc).  Inference only: eval mode, no gradients."""
+        if self.training:
+            from trajsde_amd import _lib
+            raise _lib.TrajsdeError("SDEDecoder.sample is inference only: call model.eval() first")
+        return self._rt.decoder_forward_mc(data, local_embed, global_embed, n_samples, noise=noise, sample_stride=sample_stride,
+                                           return_samples=return_samples)

@@ -117,6 +117,45 @@ class PredictionModelSDENet(GlueBase):
             out["diff_in"], out["diff_out"], out["label_in"], out["label_out"] = diff_in, diff_out, label_in, label_out
         return out
 
+    @torch.no_grad()
+    def predict_samples(self, data, n_samples: int, noise: Optional["runtime.NoiseSpec"] = None, return_samples: bool = False,
+                        sample_stride: Optional[int] = None):
+        """forward() with `n_samples` draws of the DECODER's noise for every (mode, actor) instead of one: graph stage, encoder and
+        global interactor run once, the decoder solves all samples in one launch (SDEDecoder.sample) and reduces them on the device.
+        Returns forward()'s dict -- `loc` is sample 0, bit for bit forward(data, noise)'s `loc`; `pi`, `reg_mask`, `diff_*` / `label_*`
+        or `stds` as there -- plus `loc_mean` [K,N,T,4], `loc_cov` [K,N,T,3] (unbiased var_x, var_y, cov_xy) and, with `return_samples`,
+        `samples` [R,K,N,T,4].  The encoder's noise is drawn once (forward_ood covers the latent side).  Eval mode only; no host
+        synchronisation; `noise.seed_dev` is honoured.  `sample_stride`: runtime.StageRuntime.decoder_forward_mc."""
+        from trajsde_amd import _lib
+        if self.training:
+            raise _lib.TrajsdeError("predict_samples is inference only: call model.eval() first")
+        N = data["x"].shape[0]
+        runtime.mc_check_arguments(n_samples, int(self.decoder.num_modes) * N, sample_stride)      # refused before any launch
+        ood = bool(getattr(self, "ood", False))
+        noise = runtime.NoiseSpec.resolve(noise)
+        if not self.rotate:
+            raise NotImplementedError("rotate=False is not built (shipped config: rotate: true, CFG:18)")
+        runtime._require_gpu(data["x"], "the batch (predict_samples)")
+        self._ensure_rotated(data)
+        prepared = None
+        if ood:
+            local_embed, stds = self.encoder.forward_ood(data=data, noise=noise)
+        else:
+            rt = getattr(self.aggregator, "_rt", None)
+            side = rt.arm_rel_prefetch(data, self.encoder) if rt is not None else None
+            local_embed, diff_in, diff_out, label_in, label_out = self.encoder(data=data, noise=noise,
+                                                                               preserve_side_effects=getattr(self, "preserve_side_effects", None))
+            prepared = rt.launch_rel_prefetch(data, side) if side is not None else None
+        global_embed = (self.aggregator(data=data, local_embed=local_embed, noise=noise, prepared=prepared) if prepared is not None
+                        else self.aggregator(data=data, local_embed=local_embed, noise=noise))
+        out = self.decoder.sample(data, local_embed, global_embed, n_samples, noise=noise, sample_stride=sample_stride,
+                                  return_samples=return_samples)
+        if ood:
+            out["stds"] = stds
+        else:
+            out["diff_in"], out["diff_out"], out["label_in"], out["label_out"] = diff_in, diff_out, label_in, label_out
+        return out
+
     @staticmethod
     def check_range() -> None:
         """raise if a launch since the last check left the fp16 range of the split-precision products (csrc/range.hpp);

@@ -409,6 +409,34 @@ def _loc4(out: dict) -> torch.Tensor:
     return loc.contiguous()
 
 
+def mc_check_arguments(n_samples, rows: int, sample_stride=None) -> Tuple[int, int]:
+    """(R, D) of a Monte-Carlo decode over `rows` = K * N paths, or the refusal the entry point would give: R >= 2 (one sample is the
+    plain forward), D >= 1 (default: `rows`) and (R - 1) * D + rows <= 2^32 -- the Philox counter row is 32 bits"""
+    R = int(n_samples)
+    if R != n_samples or R < 2:
+        raise _lib.TrajsdeError(f"n_samples must be an integer >= 2, got {n_samples!r} (one sample is the plain forward)")
+    if R > _lib.MC_MAX_SAMPLES:
+        raise _lib.TrajsdeError(f"n_samples {R} is above {_lib.MC_MAX_SAMPLES}")
+    stride = int(rows) if sample_stride is None else int(sample_stride)
+    if stride < 1 or (R - 1) * stride + int(rows) > 2 ** 32:
+        raise _lib.TrajsdeError(f"sample_stride {stride}: must be >= 1 with (n_samples - 1) * sample_stride + K * N <= 2^32 (sample s draws "
+                                f"from Philox counter row id + s * sample_stride, a 32-bit word); got ({R} - 1) * {stride} + {int(rows)}")
+    return R, stride
+
+
+def mc_statistics_host(samples: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the torch twin of the device reduction of decoder_forward_mc, in float64: `samples` [R, ..., C] (C >= 2: x, y, ...) ->
+    (sample mean [..., C], unbiased sample covariance of (x, y) [..., 3]: var_x, var_y, cov_xy)"""
+    if samples.dim() < 2 or samples.shape[0] < 2 or samples.shape[-1] < 2:
+        raise _lib.TrajsdeError(f"samples must be [R >= 2, ..., C >= 2], got {tuple(samples.shape)}")
+    x = samples.detach().to(torch.float64)
+    mean = x.mean(dim=0)
+    d = x[..., :2] - mean[..., :2]
+    u = 1.0 / (x.shape[0] - 1)
+    cov = torch.stack([(d[..., 0] ** 2).sum(0), (d[..., 1] ** 2).sum(0), (d[..., 0] * d[..., 1]).sum(0)], dim=-1) * u
+    return mean, cov
+
+
 class PackSet:
     """The weight images of several (StageRuntime, stage id) pairs packed by ONE call (trajsde_pack_weights_many: three launches
     over a job table that stays on the device).  A training step re-packs six images after every optimizer step -- 26 launches and 6
@@ -703,6 +731,55 @@ class StageRuntime:
                              loc.data_ptr(), pi.data_ptr(), _stream()), name)
         out = {"loc": loc, "pi": pi, "reg_mask": ~data["padding_mask"][:, -T:]}          # DEC:104
         _drop_scale_channels(m, out)
+        return out
+
+    def decoder_forward_mc(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, n_samples: int,
+                           noise: Optional[NoiseSpec] = None, sample_stride: Optional[int] = None,
+                           return_samples: bool = False) -> Dict[str, torch.Tensor]:
+        """Monte-Carlo decoding (include/trajsde_hip_mc.h): `n_samples` = R >= 2 sample paths of every (mode, actor) from ONE y0, in one
+        launch.  Sample s of path r = k N + n is decoder_forward's solve with the Philox counter row rid(r) + s * D (uint32), D =
+        `sample_stride` (default K * N; a sharded caller passes the global row count), so sample 0 is decoder_forward's draw bit for
+        bit and sample s is its draw under NoiseSpec(seed, dec_row_ids=ids + s * D).  With `noise.dec_row_ids` the ids stay on the
+        device: the caller keeps max(ids) + (R - 1) * D below 2^32 (checked here for local ids only).  `noise.z_dec`, if given, is
+        [n_euler, R * K * N, 64], row s * K * N + r.  Returns `loc` (sample 0, as decoder_forward returns it: the entry point's `loc0`
+        output, no second solve), `pi`, `reg_mask`, `loc_mean` [K,N,T,4] (sample mean of x, y, scale_x, scale_y), `loc_cov` [K,N,T,3]
+        (unbiased var_x, var_y, cov_xy) and, with `return_samples`, `samples` [R,K,N,T,4].  `uncertain: False` drops the scale channels
+        of `loc`, `loc_mean` and `samples`.  No host synchronisation; `noise.seed_dev` is honoured."""
+        m = self.module
+        K, T = int(m.num_modes), int(m.future_steps)
+        N = local_embed.shape[0]
+        R, stride = mc_check_arguments(n_samples, K * N, sample_stride)
+        noise = NoiseSpec.resolve(noise)
+        _require_gpu(local_embed, "local_embed")
+        dev = local_embed.device
+        sched, step_tab, out_tab = self._decoder_tables(T, dev)
+        if noise.z_dec is not None and tuple(noise.z_dec.shape) != (sched.n_euler, R * K * N, D):
+            raise _lib.TrajsdeError(f"z_dec must be [{sched.n_euler},{R * K * N},{D}] (n_samples * K * N rows per Euler step, sample-major)")
+        L = _lib.lib()
+        milstein = m.method == "milstein"
+        blob = self.blob(_lib.STAGE_DECODER_MILSTEIN) if milstein else self.blob()
+        loc = torch.empty(K, N, T, 4, device=dev, dtype=torch.float32)
+        loc_mean = torch.empty(K, N, T, 4, device=dev, dtype=torch.float32)
+        loc_cov = torch.empty(K, N, T, 3, device=dev, dtype=torch.float32)
+        samples = torch.empty(R, K, N, T, 4, device=dev, dtype=torch.float32) if return_samples else None
+        pi = torch.empty(N, K, device=dev, dtype=torch.float32)
+        ws_bytes = self._checked_ws_bytes("trajsde_decoder_mc_ws_bytes", N, K, T, R)
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        cn = noise.c_noise(noise.z_dec, noise.dec_row_ids)
+        with torch.cuda.device(dev):
+            _lib.check(L.trajsde_decoder_forward_mc(N, K, T, 1 if milstein else 0, blob.data_ptr(), local_embed.contiguous().data_ptr(),
+                                                    global_embed.contiguous().data_ptr(), step_tab.data_ptr(), sched.n_euler,
+                                                    out_tab.data_ptr(), float(m.min_scale), C.byref(cn), R, stride, ws.data_ptr(), ws_bytes,
+                                                    loc_mean.data_ptr(), loc_cov.data_ptr(), _ptr(samples), loc.data_ptr(), pi.data_ptr(),
+                                                    _stream()), "trajsde_decoder_forward_mc")
+        out = {"loc": loc, "pi": pi, "reg_mask": ~data["padding_mask"][:, -T:], "loc_mean": loc_mean, "loc_cov": loc_cov}
+        if samples is not None:
+            out["samples"] = samples
+        _drop_scale_channels(m, out)
+        if not getattr(m, "uncertain", True):
+            out["loc_mean"] = loc_mean[..., :2].contiguous()
+            if samples is not None:
+                out["samples"] = samples[..., :2].contiguous()
         return out
 
     def decoder_nll_backward(self, data, local_embed: torch.Tensor, global_embed: torch.Tensor, out: Dict[str, torch.Tensor],
