@@ -1716,6 +1716,12 @@ class CapacityBuffers:
     `buf.batch` keeps its tensors' shapes and addresses over every `stage()`; `buf.noise(seed)` keys the three noise streams by the
     row-id tables, so the real rows (`[:N]` of loc / pi / reg_mask, `[:S]` of diff_in / diff_out) draw the noise of the unpadded
     batch.  Every call overwrites every element of every tensor and table: a smaller batch after a larger one leaves nothing behind.
+    Monte-Carlo decoding keys sample s by `row id + s * sample_stride`, and its default stride is K * N of the tensor it is handed --
+    K * N_padded here, under which only sample 0 is the unpadded call's.  `buf.sample_stride` is K * N of the batch staged last (from
+    its shape: no device read; None before the first `stage()`):
+        out = model.predict_samples(buf.batch, R, noise=buf.noise(seed), sample_stride=buf.sample_stride)
+    gives every sample of the unpadded `model.predict_samples(batch, R, noise=NoiseSpec(seed=seed))` on the real rows.  (The ids of the
+    real rows of sample s >= 1 then coincide with ids of PAD rows of earlier samples, never with another real (row, sample).)
     Refused with a message: a host tensor or one on another device among the batch's, a batch that does not fit (`why_not`), other
     time slots or points per lane.
     The forward REBINDS `buf.batch.y` to its rotated copy (MODEL:83-84): `stage()` puts the static tensor back."""
@@ -1741,6 +1747,7 @@ class CapacityBuffers:
         self.batch = empty.to(self.device)
         self._y = self.batch.y
         self.ids = {k: v.to(self.device) for k, v in ids.items()}
+        self.sample_stride: Optional[int] = None          # K * N of the batch staged last (predict_samples' sample_stride)
         keep = []
         self._dst = _c_batch(self.batch, keep=keep)
         # the launch writes through these addresses on every stage(): each must be the static tensor's own, not a converted copy's
@@ -1793,6 +1800,7 @@ class CapacityBuffers:
                                                     self.radius, ids["fake_row_ids"].data_ptr(), ids["enc_row_ids"].data_ptr(),
                                                     ids["dec_row_ids"].data_ptr(), _stream()), "trajsde_batch_pad")
         self.batch.y = self._y
+        self.sample_stride = self.num_modes * int(batch["x"].shape[0])
         if GraphContext.KEY in self.batch:                # the launch writes in place: no version counter moves, so the graph a forward
             del self.batch[GraphContext.KEY]              # parked on the buffers would pass for current -- the next forward builds its own
 
