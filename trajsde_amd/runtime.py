@@ -488,13 +488,16 @@ class PackSet:
             # the images are re-packed IN PLACE: streams that read them since the last pack (StageRuntime.blob records them) may still
             # have kernels queued on the old contents -- the pack waits for what they hold now
             packing = torch.cuda.current_stream()
-            for rt, sid in self.entries:
+            for (rt, sid), blob in zip(self.entries, self._blobs):
                 for sid_, readers in list(rt._readers.items()):
                     if sid_ != sid:
                         continue
                     for handle, stream in readers.items():
                         if handle != packing.cuda_stream:
                             packing.wait_stream(stream)
+                    cached = rt._blobs.get(sid)
+                    if cached is not None and cached[0] is not blob:
+                        rt._retire(sid)              # an image of the stage's own is dropped below: its block stays the readers' until they are through
                     readers.clear()
             _lib.check(L.trajsde_pack_weights_many(self._items, len(self.entries), host.data_ptr(), table.data_ptr(), nbytes, self._fresh,
                                                    _stream()), "trajsde_pack_weights_many")
@@ -623,6 +626,7 @@ class StageRuntime:
             nl, K = self._dims()
             _, arr, n_tensors, n_floats = self._param_table(stage_id)
             blob = torch.empty(n_floats, device=first.device, dtype=torch.float32)
+            self._retire(stage_id)
             with torch.cuda.device(first.device):
                 _lib.check(L.trajsde_pack_weights(stage_id, nl, K, arr, n_tensors, blob.data_ptr(), n_floats, _stream()),
                            "trajsde_pack_weights")
@@ -641,6 +645,16 @@ class StageRuntime:
             elif cur.cuda_stream != packed_on:
                 cur.wait_event(ev)          # packed on another stream (multi-stream drivers): order the reads behind the pack
         return blob
+
+    def _retire(self, stage_id: int) -> None:
+        """the cached image of `stage_id` is about to be REPLACED by a new tensor: streams that read it from beside its packing stream
+        (remembered in `_readers`) may still have kernels queued on it, and they hold a raw pointer -- the caching allocator is told, so
+        that the block is not handed out again before they are through.  No host wait; the readers of the new image start afresh."""
+        readers = self._readers.pop(stage_id, None)
+        cached = self._blobs.get(stage_id)
+        if readers and cached is not None:
+            for stream in readers.values():
+                cached[0].record_stream(stream)
 
     def packs_complete(self) -> None:
         """the caller has synchronised the device: no pack is in flight, nothing left to order reads against"""
