@@ -202,6 +202,16 @@ MC_EXT_SIGNATURES = {
                                              P, I64, P, P, P, P, P, P]),
 }
 MC_MAX_SAMPLES = 65536                                    # TRAJSDE_MC_MAX_SAMPLES
+# csrc/layouts.hpp EdgeL6F (fp16x3 build): the STAGE_ENCODER blob ends with the fused edge-attention images of the AA and the AL block,
+# EDGE_FUSED_IMAGE_FLOATS each, and each of those ends with the folded key / value image MKV | CKV0 (two 64 x 64 fp16x3 images of
+# lin_k W2c and lin_v W2c, then c_k | c_v): EDGE_FOLD_IMAGE_FLOATS = 2 * 4096 + 128.  A static_assert in layouts.hpp keeps them in step.
+EDGE_FUSED_IMAGE_FLOATS, EDGE_FOLD_IMAGE_FLOATS = 31888, 8320
+
+
+def edge_fold_offsets(encoder_blob_floats: int) -> dict:
+    """{"aa" | "al": offset in floats of that block's MKV | CKV0 image inside a STAGE_ENCODER blob of `encoder_blob_floats` floats}"""
+    al = int(encoder_blob_floats) - EDGE_FOLD_IMAGE_FLOATS
+    return {"aa": al - EDGE_FUSED_IMAGE_FLOATS, "al": al}
 # the reduction's geometry (csrc/clip.hip; the workspace query returns 8 bytes per workgroup, which ties these to the library):
 # a workgroup takes CLIP_WG_FLOATS consecutive elements a pass, the grid is at most CLIP_MAX_WGS workgroups and strides beyond that
 CLIP_WG_FLOATS, CLIP_MAX_WGS = 2048, 512

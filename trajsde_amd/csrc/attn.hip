@@ -315,7 +315,15 @@ __global__ __launch_bounds__(1024 / NT) void k_edge_attn2(const float* __restric
   const int64_t E = edge_count(ec);
   const int C = stream_len(ec, E, C_host);
   if (E <= 0) return;                                      // (only reachable when the count lives on the device)
-  stage_blob(lds, img_g, EL::LDS_SIZE);
+  // FOLD (round 8, layouts.hpp EdgeL6F MKV | CKV0): the inference instantiations run lin_k | lin_v on the operand of the W2 product.
+  // Their image in LDS is the blob's with MKV in the WKV slot and c_k | c_v in the slots of AG3 | AE3, which only the tape reads.
+  constexpr bool FOLD = TSDE_EDGE_FOLD && TSDE_R6_ATOMS && TSDE_R6_SOFTMAX && !DROP && !SAVE;
+  if constexpr (FOLD) {
+    stage_copy_windows<EL::AG3, EL::AE3_END, EL::CKV0, EL::WKV, EL::WKV_END, EL::MKV>(lds, img_g, EL::LDS_SIZE);
+    __syncthreads();
+  } else {
+    stage_blob(lds, img_g, EL::LDS_SIZE);
+  }
   const Lane L;
 #if TSDE_R6_TOP
   // (the wave index as a SCALAR: with it the stream length below is one, and the loop counter and its back-edge are scalar instructions)
@@ -523,13 +531,16 @@ __global__ __launch_bounds__(1024 / NT) void k_edge_attn2(const float* __restric
       st.mark(5);
       product_x6_n<NT, 4>(emb, xh, xl, lds + EL::W2, L.lane, NoAtoms{});
       st.mark(6);
+      float q4[NT];
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const float q4 = centred_rstd(emb[t]);
+        q4[t] = centred_rstd(emb[t]);
+        if constexpr (!FOLD) {
 #pragma unroll
-        for (int jt = 0; jt < 4; ++jt)
+          for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-          for (int c = 0; c < 4; ++c) emb[t][jt][c] *= q4;     // (y - mean) * rstd of the last LayerNorm; gamma / beta live downstream
+            for (int c = 0; c < 4; ++c) emb[t][jt][c] *= q4[t];  // (y - mean) * rstd of the last LayerNorm; gamma / beta live downstream
+        }
       }
       st.mark(7);
       if (SAVE) {                                            // the tape holds the embedding rows proper
@@ -545,7 +556,11 @@ __global__ __launch_bounds__(1024 / NT) void k_edge_attn2(const float* __restric
           if (ok[t]) store_row(tr, emb_out, base_e[t] + it, L.g);
         }
       }
-      split_rows_n<NT>(xh, xl, emb);
+      // Round 8 (FOLD): the scale of that LayerNorm is a per-edge scalar and commutes with lin_k | lin_v, so the two products take the
+      // operand the W2 product already has (h' in xh / xl) on the composite image MKV = WKV W2c, start from c_k | c_v = WKV b2c, and
+      // rstd re-enters as one multiply on the logit and one on the softmax weight of each (tile, head group): no second operand
+      // split, no 16 multiplies a tile.  The embedding rows are needed for their sum of squares only.
+      if constexpr (!FOLD) split_rows_n<NT>(xh, xl, emb);
       // k / v without their constant parts (EdgeL6F): q . CK shifts all logits of a (target, head) alike, and sum_e alpha_e CV = CV
       // is added by k_seg_merge.  With attention dropout the kept weights do not sum to one, so v carries CV here.
       f4 kk[NT][4], vv[NT][4], keep[NT];
@@ -553,8 +568,13 @@ __global__ __launch_bounds__(1024 / NT) void k_edge_attn2(const float* __restric
       for (int t = 0; t < NT; ++t) {
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
-          kk[t][jt] = f4{0.f, 0.f, 0.f, 0.f};
-          vv[t][jt] = DROP ? *reinterpret_cast<const f4*>(img_g + EL::CV + 16 * jt + 4 * L.g) : f4{0.f, 0.f, 0.f, 0.f};
+          if constexpr (FOLD) {                              // c_k | c_v sit in the AG3 | AE3 slots of this image (staged above)
+            kk[t][jt] = *reinterpret_cast<const f4*>(lds + EL::AG3 + 16 * jt + 4 * L.g);
+            vv[t][jt] = *reinterpret_cast<const f4*>(lds + EL::AE3 + 16 * jt + 4 * L.g);
+          } else {
+            kk[t][jt] = f4{0.f, 0.f, 0.f, 0.f};
+            vv[t][jt] = DROP ? *reinterpret_cast<const f4*>(img_g + EL::CV + 16 * jt + 4 * L.g) : f4{0.f, 0.f, 0.f, 0.f};
+          }
         }
         keep[t] = DROP ? drop_attn_row(drop, uint32_t(d[t]), uint32_t(int(base_e[t] + it) - rank0[t]), L.g, heads) : one4;
       }
@@ -567,12 +587,14 @@ __global__ __launch_bounds__(1024 / NT) void k_edge_attn2(const float* __restric
           constexpr int a = i / per, t = a >> 2, jt = a & 3;
           const f4 qv = *reinterpret_cast<const f4*>(qs + ((4 * t + jt) * 64 + L.lane) * 4);
           float lg = head_logit1(qv, kk[t][jt], heads);
+          if constexpr (FOLD) lg *= q4[t];                   // k = rstd (M_k h' + c_k)
           // Branch-free: a row beyond the list (the tail of the last stream; rows of streams >= nstreams) enters with logit -inf --
           // weight 2^(-inf) = 0, running maximum and scale unchanged.  A row that never had an edge turns its state into NaNs
           // (2^(-inf + inf)); it is never flushed (cur < 0).
           if (!ok[t]) lg = -INFINITY;
           float sc1, exk1;
           seg_front1(S[t], jt, lg, keep[t][jt], sc1, exk1);
+          if constexpr (FOLD) exk1 *= q4[t];                 // w v = (w rstd) (M_v h' + c_v)
           seg_scale1(S[t], jt, sc1);
           sc[t][jt] = sc1;
           exk[t][jt] = exk1;

@@ -85,6 +85,11 @@ struct EdgeL6 {
 //   CK = lin_k(beta3), CV = lin_v(beta3) (biases included) are the constant parts of k and v.  q . CK is the same for every
 //     edge of a (target, head): the softmax does not see it (it is added back to the saved maximum of the training tape),
 //     and sum_e alpha_e CV = CV is added once per target by k_seg_merge.  Both are read from the blob in global memory.
+//   MKV | CKV0 (round 8, TSDE_EDGE_FOLD): the last LayerNorm's scale folded THROUGH lin_k | lin_v.  Its only non-linearity is the
+//     per-edge scalar rstd, and a scalar commutes with a linear map:  WKV (rstd emb_c) = rstd (MKV h' + CKV0)  with
+//     MKV = WKV W2c (128 x 64), CKV0 = WKV b2c (c_k | c_v), formed in double from the raw parameters (pack.hip PK_MAT6_FOLD).  The
+//     inference instantiations of k_edge_attn2 stage MKV into the WKV slot of LDS and CKV0 into the AG3 | AE3 slot (which only the
+//     tape needs), so the image in LDS keeps its size; the tape / dropout instantiations and everything else read the plain WKV.
 struct EdgeL6F {
   enum : int {
     S_END = 0,
@@ -97,9 +102,17 @@ struct EdgeL6F {
     TS_FIELD(A_F, IN2F, WKV), TS_FIELD(B_F, IN2F, A_F),                 // the two first layers as matrix-core fragments (below)
     LDS_SIZE = B_F_END,
     TS_FIELD(CK, 64, B_F), TS_FIELD(CV, 64, CK),
-    SIZE = CV_END
+    TS_FIELD(MKV, 2 * MAT64X6, CV), TS_FIELD(CKV0, 128, MKV),
+    SIZE = CKV0_END
   };
 };
+static_assert(EdgeL6F::AE3_END - EdgeL6F::AG3 == 128 && EdgeL6F::AE3_END == EdgeL6F::A_C && EdgeL6F::MKV % 4 == 0,
+              "the folded image stages CKV0 over AG3 | AE3 and MKV over WKV in 16-byte steps");
+#if TSDE_SPLIT_H3
+// trajsde_amd/_lib.py EDGE_FUSED_IMAGE_FLOATS / EDGE_FOLD_IMAGE_FLOATS: the encoder blob ends with the AA and the AL image, each ending
+// with MKV | CKV0 -- which is how the tests find them from trajsde_blob_floats alone
+static_assert(EdgeL6F::SIZE == 31888 && EdgeL6F::SIZE - EdgeL6F::MKV == 8320, "keep trajsde_amd/_lib.py in step");
+#endif
 // the embedding part of EdgeL6F alone (the global interactor's relative-pose embedding, attn.hip k_edge_embed2): the same centred
 // matrices and matrix-core first layers, no key / value image; AG3 | AE3 are applied by the kernel (its output IS the LayerNorm's)
 struct EdgeL6G {

@@ -43,7 +43,7 @@ struct PackJob {
   const float *src, *src2, *src3;
   float* dst;
 };
-enum PackKind { PK_VEC = 0, PK_COL, PK_MAT, PK_MAT_PAD, PK_MATT, PK_MAT6, PK_MAT6_STACK2, PK_SPLIT, PK_LN2, PK_MAT6_CENTRED, PK_VEC_CENTRED, PK_AFFINE, PK_IN2F };
+enum PackKind { PK_VEC = 0, PK_COL, PK_MAT, PK_MAT_PAD, PK_MATT, PK_MAT6, PK_MAT6_STACK2, PK_SPLIT, PK_LN2, PK_MAT6_CENTRED, PK_VEC_CENTRED, PK_AFFINE, PK_IN2F, PK_MAT6_FOLD, PK_VEC_FOLD };
 constexpr int PACK_JOBS_PER_LAUNCH = 48;        // 48 x 64 B: under the 4 KB kernel-argument limit
 struct PackJobs {
   PackJob j[PACK_JOBS_PER_LAUNCH];
@@ -177,6 +177,36 @@ __device__ __forceinline__ void k_pack_affine(int i, const float* __restrict__ W
   dst[i] = float(acc);
 }
 
+// The last LayerNorm's scale folded through the layer behind it (layouts.hpp EdgeL6F MKV | CKV0): with W2c the feature-centred matrix
+// of k_pack_mat6_centred and b2c the centred bias,  W diag(gamma) (rstd (W2c h + b2c)) = rstd (M h + c)  for
+//   M = W diag(gamma) W2c   (64 x 64, this job: the image of k_pack_mat6 for one of lin_k / lin_v)
+//   c = W diag(gamma) b2c   (k_pack_vec_fold)
+// Every element is formed in double from the raw parameters and rounded once, then split: the pieces are those of the composite,
+// not of a product of pieces.
+__device__ __forceinline__ void k_pack_mat6_fold(int i, const float* __restrict__ W, const float* __restrict__ gamma,
+                                                 const float* __restrict__ w2, unsigned short* __restrict__ dst) {
+  const int per_plane = 4 * 2 * 512;
+  if (i >= per_plane) return;
+  const int j = i & 7, lane = (i >> 3) & 63, s = (i >> 9) % 2, jo = (i >> 9) / 2;
+  const int row = 16 * jo + (lane & 15), col = 32 * s + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
+  double m = 0;
+  for (int r = 0; r < 64; ++r) m += w2[r * 64 + col];
+  m /= 64;
+  double acc = 0;
+  for (int r = 0; r < 64; ++r) acc += double(W[row * 64 + r]) * double(gamma[r]) * (double(w2[r * 64 + col]) - m);
+  store_split(float(acc), dst, i, per_plane);
+}
+__device__ __forceinline__ void k_pack_vec_fold(int i, const float* __restrict__ W, const float* __restrict__ gamma,
+                                                const float* __restrict__ b2, float* __restrict__ dst) {
+  if (i >= 64) return;
+  double m = 0;
+  for (int r = 0; r < 64; ++r) m += b2[r];
+  m /= 64;
+  double acc = 0;
+  for (int r = 0; r < 64; ++r) acc += double(W[i * 64 + r]) * double(gamma[r]) * (double(b2[r]) - m);
+  dst[i] = float(acc);
+}
+
 // closed-form Linear(2,64)->LayerNorm block (layouts.hpp In2L) from W [64][2], b [64], gamma [64]: thread f < 64 writes
 // the gamma-scaled centred columns, thread 0 the Cholesky factor of their Gram matrix / 64; sums in double
 __device__ __forceinline__ void k_pack_ln2(int i, const float* __restrict__ W, const float* __restrict__ b,
@@ -245,6 +275,8 @@ __device__ __forceinline__ void pack_element(const PackJob& J, int i) {
     case PK_VEC_CENTRED: k_pack_vec_centred(i, J.src, J.src2, J.dst); break;
     case PK_AFFINE: k_pack_affine(i, J.src, J.src2, J.src3, J.dst); break;
     case PK_LN2: k_pack_ln2(i, J.src, J.src2, J.src3, J.dst); break;
+    case PK_MAT6_FOLD: k_pack_mat6_fold(i, J.src, J.src2, J.src3, reinterpret_cast<unsigned short*>(J.dst)); break;
+    case PK_VEC_FOLD: k_pack_vec_fold(i, J.src, J.src2, J.src3, J.dst); break;
     case PK_IN2F: k_pack_in2f(i, J.src, J.src2, reinterpret_cast<unsigned short*>(J.dst)); break;
     case PK_SPLIT: k_pack_split(i, J.src, reinterpret_cast<unsigned short*>(J.dst), J.p0, J.p1, J.p2, J.p3, J.p4 & 0x3FFFFFFF, J.p4 >> 30); break;
   }
@@ -451,6 +483,14 @@ static void recipe_edge_fused(Packer& P, const std::string& p, const std::string
   P.jobs.back().src3 = bk;
   P.emit(PK_AFFINE, 64, wv, d + E::CV, 0, 0, 0, 0, 0, e3);
   P.jobs.back().src3 = bv;
+  // the composite of W2 and lin_k | lin_v for the inference stream (TSDE_EDGE_FOLD); the plain WKV above stays for the tape forms
+  const float* const wkv[2] = {wk, wv};
+  for (int h = 0; h < 2; ++h) {
+    P.emit(PK_MAT6_FOLD, 4 * 2 * 512, wkv[h], d + E::MKV + h * MAT64X6, 0, 0, 0, 0, 0, g3);
+    P.jobs.back().src3 = w2;
+    P.emit(PK_VEC_FOLD, 64, wkv[h], d + E::CKV0 + 64 * h, 0, 0, 0, 0, 0, g3);
+    P.jobs.back().src3 = b2;
+  }
 }
 // the embedding half of recipe_edge_fused on the EdgeL6G image (no key / value part): the global interactor's rel_embed
 static void recipe_edge_fused_embed(Packer& P, const std::string& p, int base) {

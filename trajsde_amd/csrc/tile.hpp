@@ -42,6 +42,13 @@
 #define TSDE_R6_SPLIT 1
 #endif
 
+// round 8:
+//   TSDE_EDGE_FOLD   fused edge attention, inference: lin_k | lin_v on the operand of the W2 product through the composite image
+//                    MKV = WKV W2c (layouts.hpp EdgeL6F); 0 restores the round-7 stream (second split, rstd on the embedding rows)
+#ifndef TSDE_EDGE_FOLD
+#define TSDE_EDGE_FOLD 1
+#endif
+
 // Correctness guard (HISTORY.md section 5 item 8, trajsde_amd/build.py): built with the SLP vectoriser on, identical launches of the
 // backward tile kernels disagree in their low-order bits.  The build passes -fno-slp-vectorize together with -DTSDE_NO_SLP=1; a
 // recipe that forgets the pair stops here instead of shipping a library whose results are not reproducible.
@@ -927,6 +934,27 @@ __device__ __forceinline__ void stage_copy(float* lds, const float* blob, int n_
     dst[i + step] = b;
   }
   for (; i < n4; i += step) dst[i] = src[i];
+}
+// stage_copy of an image of which two windows come from elsewhere in the blob: floats [A0, A1) of the image are read at blob + ASRC,
+// floats [B0, B1) at blob + BSRC, the rest in place.  ONE pass with the same eight loads in flight (a copy per window would put the
+// windows' memory latencies in a row at the head of the launch); all offsets multiples of 4 floats.
+template <int A0, int A1, int ASRC, int B0, int B1, int BSRC>
+__device__ __forceinline__ void stage_copy_windows(float* lds, const float* blob, int n_floats) {
+  static_assert(A0 % 4 == 0 && A1 % 4 == 0 && ASRC % 4 == 0 && B0 % 4 == 0 && B1 % 4 == 0 && BSRC % 4 == 0 && A0 <= A1 && A1 <= B0 && B0 <= B1,
+                "16-byte steps, windows in order");
+  const f4* src = reinterpret_cast<const f4*>(blob);
+  f4* dst = reinterpret_cast<f4*>(lds);
+  const int n4 = n_floats >> 2, step = blockDim.x;
+  auto from = [](int i) { return i + ((i >= A0 / 4 && i < A1 / 4) ? (ASRC - A0) / 4 : (i >= B0 / 4 && i < B1 / 4) ? (BSRC - B0) / 4 : 0); };
+  int i = threadIdx.x;
+  for (; i + 7 * step < n4; i += 8 * step) {
+    f4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = src[from(i + u * step)];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dst[i + u * step] = v[u];
+  }
+  for (; i < n4; i += step) dst[i] = src[from(i)];
 }
 __device__ __forceinline__ void stage_blob(float* lds, const float* blob, int n_floats) {
   stage_copy(lds, blob, n_floats);
